@@ -15,10 +15,13 @@ construction -- and carries it in the line as `weak` (`--scaling weak` makes tha
 `strong`).  The data path has NO collective -- envs never interact (SURVEY.md section
 8e) -- and torch.distributed (RCCL) is used only for the barrier and the max-over-ranks time.
 
-Timing.  W untimed warm-up steps, one untimed calibration replay, then the timed region: a hipGraph holding a whole
-number of K-step blocks is replayed until the region is >= 50 ms (a K-step region alone would be ~0.5 ms at the
-driver's K = 20); `ms_per_step` = region / steps in it, `timed_steps` says how many that was.  The region is bracketed by
-barrier + torch.cuda.synchronize() on both sides, max over ranks.
+Timing.  W untimed warm-up steps, one untimed replay of each captured graph, then the timed region: exactly K steps, as
+K // c replays of a c-step hipGraph (c = min(K, 256)) and one of a (K % c)-step one; `ms_per_step` = region / K (choose K
+so that the region is long enough to time: ~20 us per step of C4).  The region is bracketed by barrier +
+torch.cuda.synchronize() on both sides, max over ranks.  The other points of the line (pipelined, weak / strong, configs)
+replay whole blocks until their own region is >= 20-50 ms.
+--dump-outputs DIR writes what the headline's last timed step returned (see dump_outputs); the inputs are seeded, so two
+runs with the same arguments step the same envs with the same actions.
 
 `value` is the LOCK-STEP path: one launch of the fused kernel per step of the whole per-GPU batch, step t+1 enqueued behind step
 t (what a policy that needs all B observations of step t before step t+1 gets; the reference's own semantics).  Beside it,
@@ -124,12 +127,15 @@ def timed_region(env, run_once, repeats, dist_barrier):
 
 def measure_steps(env, K, warmup, mode, dist_barrier, seed, min_region_ms=MIN_REGION_MS, agree=None, sub_shards=1):
     """W warm-up steps, a calibration pass, then a timed region of whole K-step blocks lasting >= min_region_ms.
+    min_region_ms=None (the headline: --steps sets the timed steps): W warm-up steps, then a timed region of exactly K steps.
     Returns dict(wall_s, event_ms, timed_steps, blocks).  `agree(n)` lets all ranks settle on one repeat count."""
     B, A, dev = env.batch, env.spec.num_agents, env.device
-    block = K * max(1, math.ceil(256 / K))                     # steps enqueued per run_once: >= 256, a multiple of K
     warm = random_actions(max(warmup, 1), B, A, dev, seed + 1000)
     for t in range(warmup):
         env.step(warm[t], auto_reset=AUTO_RESET)
+    if min_region_ms is None:
+        return exact_steps(env, K, mode, dist_barrier, seed, sub_shards)
+    block = K * max(1, math.ceil(256 / K))                     # steps enqueued per run_once: >= 256, a multiple of K
     acts = random_actions(block, B, A, dev, seed)
     if mode == "graph":
         graph = capture_steps(env, acts, sub_shards)
@@ -144,6 +150,51 @@ def measure_steps(env, K, warmup, mode, dist_barrier, seed, min_region_ms=MIN_RE
         repeats = agree(repeats)
     wall_s, ev_ms = timed_region(env, run_once, repeats, dist_barrier)
     return {"wall_s": wall_s, "event_ms": ev_ms, "timed_steps": block * repeats, "block": block, "repeats": repeats}
+
+
+def exact_steps(env, K, mode, dist_barrier, seed, sub_shards=1, chunk=256):
+    """A timed region of exactly K steps (after the caller's warm-up).  graph: K // c replays of a c-step hipGraph, c = min(K,
+    chunk), and one of a (K % c)-step graph, each graph replayed once untimed first (its first replay uploads it); eager: K
+    env.step calls.  The actions of step t are those of step t % c."""
+    B, A, dev = env.batch, env.spec.num_agents, env.device
+    c = min(K, chunk)
+    acts = random_actions(c, B, A, dev, seed)
+    if mode == "graph":
+        full = capture_steps(env, acts, sub_shards)
+        rest = capture_steps(env, acts[:K % c], sub_shards) if K % c else None
+        for g in (full, rest):
+            if g is not None:
+                g.replay()
+
+        def run_once():
+            for _ in range(K // c):
+                full.replay()
+            if rest is not None:
+                rest.replay()
+    else:
+        def run_once():
+            for t in range(K):
+                env.step(acts[t % c], auto_reset=AUTO_RESET)
+    wall_s, ev_ms = timed_region(env, run_once, 1, dist_barrier)
+    return {"wall_s": wall_s, "event_ms": ev_ms, "timed_steps": K, "block": c, "repeats": K // c}
+
+
+def dump_outputs(env, out_dir, budget=60 << 20):
+    """--dump-outputs: what the timed path's last step returned -- env.step's (obs, dir, reward, terminated, truncated), the env's
+    output buffers -- as <name>.npy in float32 (reward: float64, its own type).  `obs` holds the envs listed in obs_env_index.npy:
+    all of them, or a fixed, seeded sample when they would not fit in `budget` bytes beside the other arrays."""
+    torch.cuda.synchronize(env.device)
+    out = {k: getattr(env, k).cpu().numpy() for k in ("dir", "reward", "terminated", "truncated")}
+    out = {k: v.astype(np.float64 if v.dtype == np.float64 else np.float32) for k, v in out.items()}
+    B = env.batch
+    per_env = env.obs[0].numel() * 4 + 8                      # float32 observations + the float64 index
+    n = min(B, (budget - sum(v.nbytes for v in out.values())) // per_env)
+    idx = np.arange(B) if n == B else np.sort(np.random.default_rng(0).choice(B, n, replace=False))
+    out["obs"] = env.obs[torch.from_numpy(idx).to(env.device)].cpu().numpy().astype(np.float32)
+    out["obs_env_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 def kernel_time_ms(fn, iters, device, warm=30):
@@ -729,7 +780,14 @@ def main():
     ap.add_argument("--no-pipelined", action="store_true",
                     help="skip the sub-sharded variant beside the headline (profiling: its launches are instances of the same kernel "
                          "at half the batch and would mix into the kernel's rocprofv3 statistics)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last of them returned (obs -- a seeded sample of the envs --, dir, "
+                         "reward, terminated, truncated) as DIR/<name>.npy, float32 / float64; --gpus 1 only")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs writes one GPU's outputs: --gpus 1 only")
     global AUTO_RESET
     AUTO_RESET = not args.no_auto_reset
 
@@ -780,9 +838,10 @@ def main():
     env = wl.make_env(device, auto_reset=AUTO_RESET)
     hint = int(all_max(float(env.sub_shards_hint(AUTO_RESET))))          # the product's policy (mgx_sub_shards), same on all ranks
     P = 1 if args.mode != "graph" else (args.sub_shards or hint)
-    m = measure_steps(env, args.steps, args.warmup, args.mode, barrier, seed=1234 + rank,
-                      agree=lambda n: int(all_max(float(n))), sub_shards=P)
+    m = measure_steps(env, args.steps, args.warmup, args.mode, barrier, seed=1234 + rank, min_region_ms=None, sub_shards=P)
     env.check_errors()
+    if args.dump_outputs:
+        dump_outputs(env, args.dump_outputs)
     wall_max = all_max(m["wall_s"])
     wall_min = -all_max(-m["wall_s"])
     S = m["timed_steps"]
@@ -809,8 +868,10 @@ def main():
                    "auto_reset": ("fused into the step launch (mgx_step_autoreset): envs that are done restart from the "
                                   "layout pool before the next step") if AUTO_RESET else False,
                    "layout_pool": int(wl.pool[0].shape[0]),
-                   "timing": f"{m['repeats']} x {m['block']}-step {'hipGraph replays' if args.mode == 'graph' else 'eager blocks'} "
-                             f"(whole multiples of --steps) after {args.warmup} warm-up steps and one calibration pass"},
+                   "timing": (f"--steps {S} timed steps: {m['repeats']} replays of a {m['block']}-step hipGraph"
+                              + (f" and one of a {S % m['block']}-step hipGraph" if S % m["block"] else "")
+                              + f", after {args.warmup} warm-up steps and one untimed replay of each graph"
+                              if args.mode == "graph" else f"--steps {S} timed env.step calls after {args.warmup} warm-up steps")},
     }
     if not valid:
         out["valid"] = False

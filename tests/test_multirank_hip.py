@@ -1,7 +1,9 @@
 """The multi-rank path on the REAL kernels: two `torch.distributed.run` ranks each step their shard of C4 (65536 envs,
 strong-scaled: 32768 per rank) on the HIP backend; concat(shards) must equal one process stepping the whole batch.  The
 single-GPU test box has one device, so both ranks use device 0 (MGX_BENCH_ONE_GPU=1, gloo for the rendezvous) -- the code
-path is the one bench.py --gpus N runs, minus RCCL's barrier.  Also: bench.py itself under 2 ranks prints its line."""
+path is the one bench.py --gpus N runs, minus RCCL's barrier.  Also: bench.py itself under 2 ranks prints its line.
+The eight-rank runs need eight devices (one rank per GPU): eight ranks beside the test process on ONE device are more processes
+than a shared GPU may have open at once, so on a smaller node they skip before they start anything."""
 import json
 import os
 import socket
@@ -22,8 +24,19 @@ def _free_port():
         return s.getsockname()[1]
 
 
+def _need_gpus(n):
+    """Skip (before any work) unless `n` devices are visible: n ranks on one device would be n + 1 processes on it."""
+    have = torch.cuda.device_count()
+    if have < n:
+        pytest.skip(f"needs {n} GPUs (one per rank), found {have}")
+
+
 def _torchrun(args, extra_env=None, timeout=900, nproc=2):
-    env = dict(os.environ, MGX_BENCH_ONE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0", **(extra_env or {}))
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", **(extra_env or {}))
+    if nproc <= 2:
+        env["MGX_BENCH_ONE_GPU"] = "1"                  # both ranks on device 0
+    else:
+        env.pop("MGX_BENCH_ONE_GPU", None)              # one rank per device (the caller checked _need_gpus)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port())] + args
     return subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd=ROOT, env=env)
@@ -32,6 +45,8 @@ def _torchrun(args, extra_env=None, timeout=900, nproc=2):
 @pytest.mark.parametrize("name,G,T,N", [("c4", 65536, 12, 2), ("c3", 16384, 12, 2), ("c5", 2048, 6, 2), ("c4", 65536, 8, 8)])
 def test_hip_ranks_equal_single_process(tmp_path, name, G, T, N):
     """N ranks (2, and the 8 of the named 8-GPU target: 8192 envs of C4 each) == one process stepping the whole batch."""
+    if N > 2:
+        _need_gpus(N)
     out = _torchrun([os.path.join(ROOT, "tests", "shard_worker.py"), name, str(G), str(T), str(tmp_path)], nproc=N)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -83,10 +98,10 @@ def test_bench_under_two_ranks_weak_line_carries_the_strong_point():
 
 
 def test_bench_under_eight_ranks_prints_the_8_gpu_line():
-    """`bench.py --gpus 8` as the driver launches it (one rank per GPU; here all eight on device 0): the first real SCALE run
-    must not fail on plumbing.  The headline is the shape the north star's 1e8 agent-steps/s target is stated on: the 65 536 envs
-    of C4 split over the eight ranks (8192 each, the shape-specialised latency kernel); 65 536 envs on every rank ride along
-    as `weak`."""
+    """`bench.py --gpus 8` as the driver launches it (one rank per GPU): the first real SCALE run must not fail on plumbing.
+    The headline is the shape the north star's 1e8 agent-steps/s target is stated on: the 65 536 envs of C4 split over the
+    eight ranks (8192 each, the shape-specialised latency kernel); 65 536 envs on every rank ride along as `weak`."""
+    _need_gpus(8)
     out = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "5"], nproc=8, timeout=1500)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -105,8 +120,9 @@ def test_bench_under_eight_ranks_prints_the_8_gpu_line():
 def test_plain_bench_gpus_8_launches_itself():
     """`python bench.py --gpus 8` WITHOUT a launcher (how the driver's 1-GPU BENCH command would read with N swapped in): bench.py
     becomes the launcher (torch.distributed.run, 127.0.0.1) and rank 0 prints the same one line."""
-    env = dict(os.environ, MGX_BENCH_ONE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+    _need_gpus(8)
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    for k in ("MGX_BENCH_ONE_GPU", "WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "5"],
                          capture_output=True, text=True, timeout=1500, cwd=ROOT, env=env)
