@@ -280,7 +280,9 @@ int mgx_one_hot(const uint8_t *cells, int64_t n_cells, const int32_t *dim_sizes,
 
 /* Replaces FullyObsWrapper.observation (multigrid/wrappers.py:48-58): out u8[B, W, H, 3] = Grid.state ([x][y], the
  * reference's own orientation) with every agent's (10, color, dir) written at its position in index order,
- * terminated agents included. */
+ * terminated agents included.  One env's cells and output are staged in 64 KiB of LDS: MGX_ERR_UNSUPPORTED when
+ * (cell_bytes + 3) * W * H + 96 > 65536 (cell_bytes 1 / 2 / 3: squares up to 127 / 114 / 104);
+ * BatchedMultiGridEnv.full_obs builds larger grids' tensor from the unpacked grid instead. */
 int mgx_full_obs(const MgxSpec *spec, int64_t batch, const MgxCell *grid, const uint8_t *agents, uint8_t *out,
                  void *stream);
 

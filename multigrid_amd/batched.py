@@ -17,8 +17,8 @@ import os
 import numpy as np
 import torch
 
-from . import layouts, rng as rnglib
-from .constants import NO_ACTION, Action
+from . import _lib, layouts, rng as rnglib
+from .constants import NO_ACTION, Action, Type
 from .spec import EnvSpec
 
 INT32_MAX = 2 ** 31 - 1
@@ -688,7 +688,22 @@ class BatchedMultiGridEnv:
         if getattr(self, "_full", None) is None:
             self._full = torch.zeros((self.batch, self.spec.width, self.spec.height, 3), dtype=torch.uint8,
                                      device=self.device)
-        self.backend.full_obs(self.batch, self.cells, self.agents, self._full)
+        try:
+            self.backend.full_obs(self.batch, self.cells, self.agents, self._full)
+        except _lib.MgxError as e:
+            # mgx_full_obs stages one env's cells and output in 64 KiB of LDS: (cb + 3) * W * H + 96 bytes, which refuses sides
+            # beyond 114 / 127 / 104 on 16-bit / compact / byte cells where the step runs up to 255.  Those
+            # grids get the same tensor from the unpacked grid: transposed to [x][y], the state's box content masked off as in
+            # Grid.state, every agent drawn over it in index order (multigrid/wrappers.py:52-54).
+            if e.code != _lib.ERR_UNSUPPORTED:
+                raise
+            img = self.grid.permute(0, 2, 1, 3) & torch.tensor([255, 255, 3], dtype=torch.uint8, device=self.device)
+            ag = self.agents.long()
+            env = torch.arange(self.batch, device=self.device)
+            for a in range(self.spec.num_agents):
+                img[env, ag[:, a, 2], ag[:, a, 3]] = torch.stack(
+                    (torch.full_like(ag[:, a, 0], int(Type.agent)), ag[:, a, 0], ag[:, a, 1]), dim=-1).to(torch.uint8)
+            self._full.copy_(img)
         return self._full
 
     def set_layout_pool(self, grids, agents, auxs=None):

@@ -323,6 +323,7 @@ def main():
     import custom_envs       # (round 6, likewise: the RoomGrid subclass of tests/custom_envs.py)
     record_custom(custom_envs.CASES_R6)
     record_custom_steps(custom_envs.STEP_CASES_R6)
+    record_edge()            # (behind everything older for the same reason)
 
 
 def face(env, i, target_xy, carrying=None):
@@ -337,6 +338,33 @@ def face(env, i, target_xy, carrying=None):
                 env.agents[i].state.carrying = carrying
             return
     raise RuntimeError("no free side")
+
+
+def record_edge():
+    """The largest grid the product accepts (sides <= 255) with the largest view: three agents on the far
+    edges -- the last interior column, the last interior row and the far corner (the goal taken off it) -- turned to face the
+    outer wall, objects of every kind in a band along those edges, random actions.  Pins the oracle itself where the views hang
+    over the far walls, at coordinates beyond 128."""
+    colors = ["red", "green", "blue", "purple", "yellow", "grey"]
+
+    def edges(env):
+        W, H = env.width, env.height
+        env.grid.set(W - 2, H - 2, None)
+        face(env, 0, (W - 1, H // 2))
+        face(env, 1, (W // 2, H - 1))
+        env.agents[2].state.pos = (W - 2, H - 2)
+        env.agents[2].state.dir = 0
+        r = np.random.default_rng(17)
+        agent_cells = {tuple(int(v) for v in a.state.pos) for a in env.agents}
+        for x in range(1, W - 1):
+            for y in range(1, H - 1):
+                if min(W - 2 - x, H - 2 - y) >= 9 or (x, y) in agent_cells or r.random() >= 0.2:
+                    continue
+                c = colors[int(r.integers(6))]
+                env.grid.set(x, y, [Lava, lambda: Floor(c), lambda: Key(c), lambda: Ball(c), lambda: Box(c), Wall,
+                                    lambda: Door(c), lambda: Door(c, is_open=True)][int(r.integers(8))]())
+    record("empty255_a3_v15_edges", make_env("MultiGrid-Empty-8x8-v0", size=255, agents=3, agent_view_size=15), "empty", 91,
+           12, np.random.default_rng(291), edit=edges, note="largest grid and view; agents on the far edges, facing out")
 
 
 def record_hook_envs():

@@ -71,10 +71,13 @@ golden_target = golden_aux
 
 
 def random_state(spec: EnvSpec, B: int, seed: int, density: float = 0.25, terminated_p: float = 0.05,
-                 carry_p: float = 0.3, box_contents_p: float = 0.0):
+                 carry_p: float = 0.3, box_contents_p: float = 0.0, edge_agents: bool = False):
     """Random walled grids with every object type, agents on overlappable cells (possibly stacked),
     some carrying, some already terminated.  Product layout.  box_contents_p: the share of the boxes -- lying around and carried
-    -- that hold something (include/mgx.h "BOX CONTENTS": the state byte's upper bits)."""
+    -- that hold something (include/mgx.h "BOX CONTENTS": the state byte's upper bits).  edge_agents: every agent is moved to the
+    far edges -- the last interior row, the last interior column and the far corner in turn, facing the four directions in turn
+    (every pairing of the two within 12 agents) -- onto a cell made empty, so that the views hang over the grid's far walls.  Its
+    draws come from a generator of their own: the rest of the state is the one drawn without it."""
     r = np.random.default_rng(seed)
     H, W, A = spec.height, spec.width, spec.num_agents
     grid = np.zeros((B, H, W, 3), dtype=np.uint8)
@@ -119,6 +122,14 @@ def random_state(spec: EnvSpec, B: int, seed: int, density: float = 0.25, termin
     target = np.zeros((B, 16), dtype=np.uint8)               # aux (include/mgx.h); BlockedUnlockPickup: the target box
     target[:, 0] = 7
     target[:, 1] = r.integers(0, 6, size=B)
+    if edge_agents:
+        re = np.random.default_rng(seed + 3)
+        for b in range(B):
+            for a in range(A):
+                k = b * A + a
+                x, y = [(int(re.integers(1, W - 1)), H - 2), (W - 2, int(re.integers(1, H - 1))), (W - 2, H - 2)][k % 3]
+                agents[b, a, 1:4] = k % 4, x, y
+                grid[b, y, x] = (1, 0, 0)
     return dict(grid=grid, agents=agents, rng=rng, step_count=step_count, target=target)
 
 
