@@ -112,24 +112,12 @@ struct KernelArgs {
     int32_t span_base;  // -DMGX_TIMESTAMPS=1 builds: first record of this launch in g_span (tools/span_probe.py, tools/chain_overlap.py)
 };
 
-// gfx950's LDS does take a short access at any byte address (hipcc emits ds_write_b16 for an align-1 store), but measured
-// it is far slower than aligned accesses (round 1, 3-byte cells: fused step 371 us aligned, 602 us with unaligned 16-bit
-// writes in P4).  Kept for the record only.
-#ifndef MGX_UA_WRITE
-#define MGX_UA_WRITE 0
-#endif
 #ifndef MGX_EARLY_ARGS
 #define MGX_EARLY_ARGS 2     // 1: the latency family only (DMA instantiations); 2: every instantiation with views <= 7x7 (the C4
                              // throughput kernel: 18.63-18.83 -> 18.45-18.54 us, three same-box passes; 9x9 and up: the compiler crashes on it)
 #endif
 #ifndef MGX_LATE_ARGS
 #define MGX_LATE_ARGS 1
-#endif
-#ifndef MGX_P4_B16
-#define MGX_P4_B16 1
-#endif
-#ifndef MGX_P4_PERM
-#define MGX_P4_PERM 1     // P4: one v_perm_b32 per slot makes the store-ready bytes (0: the widening chain + per-store shifts of round 2)
 #endif
 #ifndef MGX_WRITELANE_NOP
 #define MGX_WRITELANE_NOP 0
@@ -210,7 +198,6 @@ typedef const uint16_t __attribute__((address_space(3))) *lds_u16_ptr;
 typedef const int8_t __attribute__((address_space(3))) *lds_i8_ptr;
 typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
 typedef const u32_unaligned __attribute__((address_space(3))) *lds_u32_ua_ptr;
-typedef uint16_t __attribute__((aligned(1))) u16_unaligned;
 
 #ifndef MGX_SLOTS_SMALL_VIEW
 #define MGX_SLOTS_SMALL_VIEW 64
@@ -283,7 +270,7 @@ constexpr int kLutBytes = 256 * 4;
 // P4/P5 staging of a round lies over the view records + the written-cell offsets (both dead once P2 has gathered the cells; a round is
 // then 8 view slots).  C4: 1488 + 2 x 9344 = 20176 bytes for 32 envs -> 8 wavefronts per CU hold 65536 envs' tiles on the chip.
 struct LdsCarve {
-    int vpw, nw, Gw, A, tile_bytes, round_bytes;   // round_bytes: P4/P5 staging of one round (obs bytes, or one-hot cell masks)
+    int vpw, nw, Gw, A, tile_bytes, round_bytes;   // round_bytes: P4/P5 staging of one round (obs bytes, obs cell dwords, or one-hot cell masks)
     bool roll;      // mgx_rollout: tile and PCG64 state live across steps (no aliasing of the tile, rng kept in LDS)
     bool has_aux;   // env kinds with hook state
     bool c8;        // compact cells: + the decode table
@@ -335,6 +322,10 @@ struct LdsCarve {
     __host__ __device__ __attribute__((always_inline)) bool slices_ok() const { return !sliced || (roll && !c8 && out_bytes() <= 20 * vpw); }
 };
 
+// P4/P5 of the one-step kernels (not the rollout / persistent ones, whose staging may lie over the view records) for views of one
+// lane pass (V <= 7): the round's staging holds one dword per cell, in the observation's cell order, after a pad of 4 dwords
+// (mgx_rules.h obs_unit; mgx_fused_body.inc P4/P5); every other kernel stages the observation's 3-byte cells
+__host__ __device__ __attribute__((always_inline)) constexpr bool obs_dword_staging(int V, bool roll) { return !roll && V * V <= 64; }
 // one_hot: the round's staging holds one 32-bit one-hot mask per cell (+ a pad dword either side) instead of 3 obs bytes
 // `round`: slots staged per P4/P5 round (kRound, or the group size of a small-group latency instantiation)
 __host__ __device__ __attribute__((always_inline)) inline LdsCarve make_carve(int W, int H, int A, int V, int Gw, int vpw, bool roll, bool has_aux,
@@ -342,8 +333,9 @@ __host__ __device__ __attribute__((always_inline)) inline LdsCarve make_carve(in
                                                int pitch = 0) {
     // (pitch: a tile whose rows and envs SHARE the WALL ring -- row pitch W - 1, env stride (W - 1)(H - 1) cells, W more at the end)
     const int tile_bytes = pitch ? (Gw * pitch * (H - 1) + W) * cb : Gw * H * W * cb;
-    return LdsCarve{vpw, (V * V + 63) / 64, Gw, A, tile_bytes, one_hot ? round * V * V * 4 + 16 : round * V * V * 3,
-                    roll, has_aux, cb == 1, ns, sliced || ns > 1};
+    // (the one-step kernels' obs staging for views of one lane pass holds a dword per cell: obs_dword_staging)
+    const int round_bytes = one_hot ? round * V * V * 4 + 16 : (obs_dword_staging(V, roll) ? round * V * V * 4 : round * V * V * 3);
+    return LdsCarve{vpw, (V * V + 63) / 64, Gw, A, tile_bytes, round_bytes, roll, has_aux, cb == 1, ns, sliced || ns > 1};
 }
 inline int cell_bytes_of(const MgxSpec &sp) { return sp.cell_bytes == 1 ? 1 : kCellBytes; }        // the LDS tile's cells
 inline int grid_cell_bytes_of(const MgxSpec &sp) { return sp.cell_bytes == 3 ? 3 : cell_bytes_of(sp); }   // the HBM tensors' cells
@@ -511,6 +503,7 @@ __device__ __forceinline__ uint32_t set_lane(uint32_t old, uint32_t sval, const 
 // their stores are dropped, so the bulk copies need neither per-lane predicates nor 64-bit VALU address arithmetic.
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *base, int bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, bytes, 0x00020000);
 }
@@ -533,7 +526,7 @@ __device__ __forceinline__ uint64_t state_is_open(uint32_t c) {
 #ifndef MGX_PACK3
 #define MGX_PACK3 1
 #endif
-template <int V> constexpr bool kPack3 = (MGX_PACK3 != 0) && (MGX_P4_B16 != 0) && (MGX_P4_PERM != 0) && (V * V > 64) && (V * V <= 128)
+template <int V> constexpr bool kPack3 = (MGX_PACK3 != 0) && (V * V > 64) && (V * V <= 128)
                                          && 3 * (V * V - 64) <= 64;
 constexpr int pack3_passes(int n) { return (n + 2) / 3; }      // remainder passes of a block of n view slots
 

@@ -1287,114 +1287,123 @@
             }
         }
     } else {
-    // ------------------------------------------------------------------ P4/P5 in rounds of kR slots:
-    // P4 masks each cell and transposes it into the obs byte layout in LDS, P5 streams the round to HBM in 16-byte vectors
-    const int64_t o0 = tv0 * (int64_t)(V2 * 3), o1 = o0 + (int64_t)NVc * V2 * 3;  // this wave's obs bytes (of step t)
-    const int out_skew0 = (int)(o0 & 15);                                       // the same for every round (rounds of 16 slots are
-    uint8_t *out_raw = L + cv.out();                                          // whole 16-byte vectors; the sliced kernels' rounds of 8
-    constexpr int kRoundBytes = kR * V2 * 3;                                // slots alternate by 8 bytes)
-#ifndef MGX_P45_PIPE
-#define MGX_P45_PIPE 0
-#endif
-    // -DMGX_P45_PIPE=1 / 2: software-pipelined rounds (round 6; views of one lane pass) -- an experiment that measured SLOWER and is
-    // off.  A round's P5 is three ds_read_b128 -> buffer_store pairs that sit behind the round's 32 queued LDS byte writes, ~900
-    // shader clocks of a wavefront waiting for the CU's LDS pipe to drain (profiles/r6_resident.txt: in-kernel stamps); this form
-    // issues the NEXT round's P4 arithmetic (readlane, perm, select: registers only) between those reads and the stores that need
-    // them, so that P4's own part of a round is just its LDS writes.  Same box, alternating runs (profiles/r6_p45_pipeline_ab.txt):
-    // C4 lock step 18.5 -> 19.5-19.6 us, the 8192-env launch 6.2 -> 6.5, the resident rollout at 49152 envs 10.3 -> 10.9, with the
-    // scheduling barriers (1) or without (2): the straight-line form interleaves every slot's three VALU instructions with its two LDS
-    // writes and keeps the LDS pipe fed evenly; batching 16 slots of arithmetic and then 32 writes makes the burst the pipe stalls on.
-    constexpr bool kPipe = (MGX_P45_PIPE != 0) && NW == 1 && !PK3 && (MGX_P4_B16 != 0) && (MGX_P4_PERM != 0) && (kRoundBytes & 1) == 0
-                           && kG4 == kR;
-    if constexpr (kPipe) {
-        const uint32_t par0 = (uint32_t)(out_skew0 + lc.q3[0]) & 1u;        // (rounds start 0 or 8 bytes off: the parity is theirs all)
-        const uint32_t sel0 = C8 ? (par0 ? 0x0c000201u : 0x0c020100u) : (par0 ? 0x0c000401u : 0x0c040100u);
-        const uint32_t sel1 = C8 ? (par0 ? 0x0c020100u : 0x0c000201u)
-                                 : (HALF ? (par0 ? 0x0c060302u : 0x0c020603u) : (par0 ? 0x0c040100u : 0x0c000401u));
-        auto p4_values = [&](const int r0, uint32_t (&cv16)[kR]) {          // the round's store-ready cells (see P4 below): VALU only
+    [[maybe_unused]] const int64_t o0 = tv0 * (int64_t)(V2 * 3), o1 = o0 + (int64_t)NVc * V2 * 3;  // this wave's obs bytes (of step t)
+    if constexpr (obs_dword_staging(V, ROLL)) {
+    // ------------------------------------------------------------------ P4/P5 in rounds of kR slots, one dword per cell (round 7):
+    // P4 masks each cell and stores it as ONE dword (type, color, state, junk) at its image position in LDS -- the same address
+    // every round, its slot in the store's immediate offset; P5 reads 4 cells per lane (ds_read_b128), packs them into 12 bytes
+    // (mgx_rules.h obs_unit: 3 v_perm_b32, 3 more when the wave's bytes do not start on a dword) and stores them with one
+    // buffer_store_dwordx3.  The 3-byte staging it replaces took two LDS stores per cell (ds_write_b16 + ds_write_b8_d16_hi: a
+    // view is an odd number of bytes, so every other cell starts at an odd address), ~8.8 LDS-pipe cycles against 4 now.
+    // (ds_write_addtid_b32 would store in 2 cycles, but at lane order: lane k holds image cell k = j*V + i, the observation's
+    // order is i*V + j, so P5 would gather 4-5 scattered dwords per lane from per-lane addresses instead of one ds_read_b128.)
+    static_assert(NW == 1 && !PK3 && !PERSIST && kR % 4 == 0, "dword staging: views of one lane pass, rounds of whole dwords");
+    uint32_t *const stg = reinterpret_cast<uint32_t *>(L + cv.out()) + 4;     // cell c of the round at stg[c]; stg[-4..-1]: pad
+    const int s_w = (int)(o0 & 3);                                              // the wave's first obs byte, within its dword
+    // ONE buffer resource for the wave: its bytes from the dword they start in; a round's offset goes into soffset
+    const __amdgpu_buffer_rsrc_t orsrc = make_rsrc(MGX_LATE(obs) + (o0 - s_w), s_w + NVc * V2 * 3);
+    constexpr int kUnits = kR * V2 / 4 + 1;                                     // 12-byte units of a round (+1: its ragged tail)
+    constexpr int kPasses = (kUnits + 63) / 64;
+    uint32_t *const d0 = stg + lc.q3[0] / 3;                                    // this lane's cell: image[i][j] = cell i*V + j
+    // P5 of a WHOLE round of a wave whose bytes start on a dword -- every round of C4, C2, C3 and C4's 8192-env share: its kR*V*V/4
+    // units are all whole, so no lane needs a bound or the ragged path, and the round's reads are all issued before the first use
+    auto p5_whole = [&](const int r0) {
+        constexpr int kWhole = kR * V2 / 4, kWP = (kWhole + 63) / 64;
+        u32x4 d[kWP];
 #pragma unroll
-            for (int sl = 0; sl < kR; ++sl) {
-                const int s = r0 + sl;
-                const uint64_t m = (V2 > 32 ? (uint64_t)(uint32_t)__builtin_amdgcn_readlane(visHi[0], s) << 32 : 0ull)
-                                 | (uint64_t)(uint32_t)__builtin_amdgcn_readlane(visLo[0], s);
-                const uint32_t x = HALF ? cell[s >> 1][0] : cell[s][0];
-                const uint32_t tc = C8 ? x : (x & 0x070f070fu), st = C8 ? x : ((x >> 12) & 0x00030003u);
-                const uint32_t pr = __builtin_amdgcn_perm(st, tc, (HALF ? (s & 1) : (sl & 1)) ? sel1 : sel0);
-                cv16[sl] = __builtin_amdgcn_inverse_ballot_w64(m) ? pr : 0u;
-            }
-        };
-        uint32_t cur[kR], nxt[kR];
+        for (int k = 0; k < kWP; ++k) {                                         // (the last pass's idle lanes read the last unit)
+            const int u = 64 * (k + 1) <= kWhole ? lane + 64 * k : min(lane + 64 * k, kWhole - 1);
+            MGX_CHECK_LDS_PTR(6, stg + 4 * u, 16);
+            d[k] = *reinterpret_cast<const u32x4 *>(stg + 4 * u);
+        }
 #pragma unroll
-        for (int sl = 0; sl < kR; ++sl) { cur[sl] = 0; nxt[sl] = 0; }
-        if (!MGX_DBG(16)) p4_values(0, cur);
+        for (int k = 0; k < kWP; ++k) {
+            uint32_t w[3];
+            obs_unit(0u, d[k].x, d[k].y, d[k].z, d[k].w, 0, w);
+            if (64 * (k + 1) <= kWhole || lane + 64 * k < kWhole)
+                __builtin_amdgcn_raw_buffer_store_b96(u32x3{w[0], w[1], w[2]}, orsrc, 12 * (lane + 64 * k), r0 * V2 * 3,
+                                                      STREAM ? MGX_OBS_AUX : MGX_OBS_AUX_CACHED);
+        }
+    };
+    // P5 of any round at r0 (a wave's last, partial one; a wave whose bytes start s = s_w bytes into a dword)
+    auto p5_round = [&](const int r0, const int s) {
+        const int roff = r0 * V2 * 3;                                           // the round's bytes, from the wave's first
+        const int ulen = s + (int)min(kR * V2 * 3, (NVc - r0) * V2 * 3);        // ... and its window of whole dwords
 #pragma unroll
-        for (int r0 = 0; r0 < VPW; r0 += kR) {
-            const int out_skew = (kRoundBytes & 15) ? ((out_skew0 + ((r0 * V2 * 3) & 15)) & 15) : out_skew0;
-            uint8_t *const outb = out_raw + out_skew;
-            if (r0 < NVc) {
-                if (!MGX_DBG(16)) {
-                    if (lc.act[0]) {
-                        uint8_t *d0 = outb + lc.q3[0];
-                        uint8_t *const d16[2] = {d0 + par0, d0 + (par0 ^ 1u)};
-                        uint8_t *const d8[2] = {d0 + 2u * (par0 ^ 1u), d0 + 2u * par0};
-#pragma unroll
-                        for (int sl = 0; sl < kR; ++sl) {
-                            MGX_CHECK_LDS_PTR(5, d0 + sl * (V2 * 3), 3);
-                            *reinterpret_cast<uint16_t *>(d16[sl & 1] + sl * (V2 * 3)) = (uint16_t)cur[sl];
-                            d8[sl & 1][sl * (V2 * 3)] = (uint8_t)(cur[sl] >> 16);
-                        }
-                    }
-                    wave_sync();
-                    if (lane >= r0 && lane < r0 + kR && lane < NVc)          // own cell := carried object (obs.py:207)
-                        store_obs_cell(outb + (lane - r0) * (V2 * 3) + ((V / 2) * V + (V - 1)) * 3, my_carry);
-                }
-                wave_sync();
-                MGX_MARK("P5");
-                const int64_t ro0 = o0 + (int64_t)r0 * (V2 * 3);
-                const int rlen = out_skew + (int)min((int64_t)kRoundBytes, o1 - ro0);
-                uint8_t *gdst = MGX_LATE(obs) + (ro0 - out_skew);
-                const __amdgpu_buffer_rsrc_t orsrc = make_rsrc(gdst, rlen);
-                constexpr int kPasses = (kRoundBytes + 15 + 1023) / 1024;
-                u32x4 pv[kPasses];
-#pragma unroll
-                for (int k = 0; k < kPasses; ++k) {
-                    const int rel = lane16 + 1024 * k;
-                    pv[k] = u32x4{0, 0, 0, 0};
-                    if (rel < rlen && !MGX_DBG(32)) {
-                        MGX_CHECK_LDS_PTR(6, out_raw + rel, 16);
-                        pv[k] = *reinterpret_cast<const u32x4 *>(out_raw + rel);
-                    }
-                }
-                if constexpr (MGX_P45_PIPE == 1) __builtin_amdgcn_sched_barrier(0);
-                if (r0 + kR < VPW) {                                          // the next round's cells, under the reads' latency
-                    if (r0 + kR < NVc && !MGX_DBG(16)) p4_values(r0 + kR, nxt);
-                }
-                if constexpr (MGX_P45_PIPE == 1) __builtin_amdgcn_sched_barrier(0);
-                if (!MGX_DBG(32)) {
-#pragma unroll
-                    for (int k = 0; k < kPasses; ++k) {
-                        const int rel = lane16 + 1024 * k;
-                        if ((rel + 16 <= rlen) & (rel >= out_skew)) {
-                            __builtin_amdgcn_raw_buffer_store_b128(pv[k], orsrc, rel, 0, PERSIST ? 16 : (STREAM ? MGX_OBS_AUX : MGX_OBS_AUX_CACHED));
-                        } else if (rel < rlen) {                                // ragged head / tail of the wave's bytes
-                            const int lo_b = max(rel, out_skew), hi_b = min(rel + 16, rlen);
-                            if ((kRoundBytes & 15) != 0 && ((lo_b | hi_b) & 7) == 0) {
-                                __builtin_amdgcn_raw_buffer_store_b64(*reinterpret_cast<const u32x2 *>(out_raw + lo_b), orsrc, lo_b, 0,
-                                                                      PERSIST ? 16 : MGX_OBS_AUX_CACHED);
-                            } else {
+        for (int k = 0; k < kPasses; ++k) {
+            const int u = lane + 64 * k, ub = 12 * u;                          // unit u: window bytes [12u, 12u + 12)
+            if (ub < ulen) {
+                MGX_CHECK_LDS_PTR(6, stg + 4 * u - 1, 20);
+                const u32x4 d = *reinterpret_cast<const u32x4 *>(stg + 4 * u);  // cells 4u .. 4u + 3
+                const uint32_t dm1 = s ? stg[4 * u - 1] : 0u;                   // cell 4u - 1
+                uint32_t w[3];
+                obs_unit(dm1, d.x, d.y, d.z, d.w, s, w);
+                if (ub >= s && ub + 12 <= ulen) {
+                    __builtin_amdgcn_raw_buffer_store_b96(u32x3{w[0], w[1], w[2]}, orsrc, ub, roff, STREAM ? MGX_OBS_AUX : MGX_OBS_AUX_CACHED);
+                } else {                                                        // the ragged head / tail of the round's bytes
+                    const int lo_b = max(s - ub, 0), hi_b = min(ulen - ub, 12);
 #pragma clang loop vectorize(disable) unroll(disable)
-                                for (int B = lo_b; B < hi_b; ++B) __builtin_amdgcn_raw_buffer_store_b8(out_raw[B], orsrc, B, 0, PERSIST ? 16 : 0);
+                    for (int B = lo_b; B < hi_b; ++B) {                         // (selects, not an indexed array: no stack object)
+                        const uint32_t x = B < 4 ? w[0] : (B < 8 ? w[1] : w[2]);
+                        __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(x >> (8 * (B & 3))), orsrc, ub + B, roff, 0);
+                    }
+                }
+            }
+        }
+    };
+#pragma unroll
+    for (int r0 = 0; r0 < VPW; r0 += kR) {
+        if (r0 < NVc) {
+            if (!MGX_DBG(16)) {
+                if (lc.act[0]) {
+                    // whole groups of kG slots, like P2 (padding slots write junk into staging space that P5 never copies):
+                    // straight-line code whose readlane -> select -> write chains overlap
+#pragma unroll
+                    for (int g0 = 0; g0 < kR; g0 += kG4) {
+                        if (r0 + g0 < NVc) {
+#pragma unroll
+                            for (int sl = g0; sl < g0 + kG4; ++sl) {
+                                const int s = r0 + sl;
+                                // (see_through_walls: the masks are all ones -- no branch, it would fence the schedule)
+                                // (a pass of at most 32 cells has no high word)
+                                const uint64_t m = (V2 > 32 ? (uint64_t)(uint32_t)__builtin_amdgcn_readlane(visHi[0], s) << 32 : 0ull)
+                                                 | (uint64_t)(uint32_t)__builtin_amdgcn_readlane(visLo[0], s);
+                                // packed cell(s) -> (type, color, state) in bytes 0-2 (cell_unpack's fields; the pair's two ANDs
+                                // and the shift are common to both of its slots); compact cells: the decoded entry already is
+                                const uint32_t x = HALF ? cell[s >> 1][0] : cell[s][0];
+                                const uint32_t c = C8 ? x : perm_b32((x >> 12) & 0x00030003u, x & 0x070f070fu, obs_stage_sel(HALF && (s & 1)));
+                                MGX_CHECK_LDS_PTR(5, d0 + sl * V2, 4);
+                                d0[sl * V2] = __builtin_amdgcn_inverse_ballot_w64(m) ? c : 0u;   // UNSEEN = (0, 0, 0)
                             }
                         }
                     }
                 }
                 wave_sync();
-                MGX_MARK("P5end");
-#pragma unroll
-                for (int sl = 0; sl < kR; ++sl) cur[sl] = nxt[sl];
+                // lane r0+sl: its agent's own cell shows the carried object (obs.py:207; always visible, obs.py:252)
+                if (lane >= r0 && lane < r0 + kR && lane < NVc) {
+                    MGX_CHECK_LDS_PTR(5, stg + (lane - r0) * V2 + (V / 2) * V + (V - 1), 4);
+                    stg[(lane - r0) * V2 + (V / 2) * V + (V - 1)] = my_carry;
+                }
             }
+            wave_sync();
+            MGX_MARK("P5");
+            if (!MGX_DBG(32)) {
+                if (s_w == 0 && r0 + kR <= NVc) p5_whole(r0);
+                else p5_round(r0, s_w);
+            }
+            wave_sync();
+            MGX_MARK("P5end");
         }
+    }
     } else {
+    // ------------------------------------------------------------------ P4/P5 in rounds of kR slots, the observation's 3-byte cells
+    // (the rollout / persistent kernels, whose staging may lie over the view records, and views of more than one lane pass):
+    // P4 masks each cell and transposes it into the obs byte layout in LDS, P5 streams the round to HBM in 16-byte vectors
+    // (round 6 tried software-pipelined rounds -- the next round's P4 arithmetic under this round's staging reads: 5-6 % slower at
+    // C4, profiles/r6_p45_pipeline_ab.txt)
+    const int out_skew0 = (int)(o0 & 15);                                       // the same for every round (rounds of 16 slots are
+    uint8_t *out_raw = L + cv.out();                                          // whole 16-byte vectors; the sliced kernels' rounds of 8
+    constexpr int kRoundBytes = kR * V2 * 3;                                // slots alternate by 8 bytes)
 #pragma unroll
     for (int r0 = 0; r0 < VPW; r0 += kR) {
         const int out_skew = (kRoundBytes & 15) ? ((out_skew0 + ((r0 * V2 * 3) & 15)) & 15) : out_skew0;
@@ -1405,14 +1414,12 @@
                 for (int it = 0; it < NW; ++it) {
                     if (lc.act[it]) {
                         uint8_t *d0 = outb + lc.q3[it];
-#if MGX_P4_B16
                         // A cell's 3 bytes go out as one ALIGNED 2-byte store + one byte store (an LDS store costs the same
                         // VGPR -> LDS transfer whatever its width, so 2 stores instead of 3).  A view is an odd number of
                         // bytes, so the parity of a cell's first byte alternates from slot to slot: even slots use [0], odd [1].
                         const uint32_t par0 = (uint32_t)(out_skew + lc.q3[it]) & 1u;
                         uint8_t *const d16[2] = {d0 + par0, d0 + (par0 ^ 1u)};                  // the 2-byte part: bytes 0-1 or 1-2
                         uint8_t *const d8[2] = {d0 + 2u * (par0 ^ 1u), d0 + 2u * par0};         // the other byte: 2 or 0
-#if MGX_P4_PERM
                         // (round 3) ONE v_perm_b32 per slot makes the register both stores read -- bytes 0-1 = the 2-byte part,
                         // byte 2 = the other byte (ds_write_b16 / ds_write_b8_d16_hi): no widening chain, no per-store shifts.
                         // Its sources are made once per PAIR of slots sharing a cell register (HALF; per slot otherwise):
@@ -1425,11 +1432,6 @@
                         const uint32_t sel[2] = {C8 ? (par0 ? 0x0c000201u : 0x0c020100u) : (par0 ? 0x0c000401u : 0x0c040100u),
                                                  C8 ? (par0 ? 0x0c020100u : 0x0c000201u)
                                                     : (HALF ? (par0 ? 0x0c060302u : 0x0c020603u) : (par0 ? 0x0c040100u : 0x0c000401u))};
-#else
-                        const uint32_t sh16[2] = {8u * par0, 8u * (par0 ^ 1u)}, sh8[2] = {16u * (par0 ^ 1u), 16u * par0};
-#endif
-#endif
-#if MGX_P4_B16 && MGX_P4_PERM
                         if constexpr (PK3) {
                             if (it == 1) {
                                 // the shared remainder passes (mgx_fused.h: kPack3): pass p of a group holds cell 64 + lane % R of
@@ -1463,7 +1465,6 @@
                                 continue;
                             }
                         }
-#endif
                         // whole groups of kG slots, like P2 (padding slots write junk into staging space that P5
                         // never copies): straight-line code whose readlane -> select -> write chains overlap
 #pragma unroll
@@ -1476,9 +1477,7 @@
                                     // (a pass of at most 32 cells has no high word)
                                     const uint64_t m = (V2 - 64 * it > 32 ? (uint64_t)(uint32_t)__builtin_amdgcn_readlane(visHi[it], s) << 32 : 0ull)
                                                      | (uint64_t)(uint32_t)__builtin_amdgcn_readlane(visLo[it], s);
-                                    [[maybe_unused]] uint8_t *d = d0 + sl * (V2 * 3);
-                                    MGX_CHECK_LDS_PTR(5, d, 3);
-#if MGX_P4_B16 && MGX_P4_PERM
+                                    MGX_CHECK_LDS_PTR(5, d0 + sl * (V2 * 3), 3);
                                     // packed cell(s) -> (type, color) bytes and the state byte (cell_unpack's fields); the pair's
                                     // two ANDs and the shift are common to both of its slots (the compiler keeps them)
                                     const uint32_t x = HALF ? cell[s >> 1][it] : cell[s][it];
@@ -1487,19 +1486,6 @@
                                     const uint32_t c = __builtin_amdgcn_inverse_ballot_w64(m) ? pr : 0u;       // UNSEEN = (0, 0, 0)
                                     *reinterpret_cast<uint16_t *>(d16[sl & 1] + sl * (V2 * 3)) = (uint16_t)c;
                                     d8[sl & 1][sl * (V2 * 3)] = (uint8_t)(c >> 16);                            // ds_write_b8_d16_hi
-#else
-                                    // packed cell -> the observation's (type, color, state) bytes
-                                    const uint32_t c = to_obs(__builtin_amdgcn_inverse_ballot_w64(m) ? slot_cell(s, it) : CELL_UNSEEN);
-#if MGX_P4_B16
-                                    *reinterpret_cast<uint16_t *>(d16[sl & 1] + sl * (V2 * 3)) = (uint16_t)(c >> sh16[sl & 1]);
-                                    d8[sl & 1][sl * (V2 * 3)] = (uint8_t)(c >> sh8[sl & 1]);
-#elif MGX_UA_WRITE
-                                    *reinterpret_cast<u16_unaligned *>(d) = (uint16_t)c;    // ds_write_b16 at any byte address
-                                    d[2] = (uint8_t)(c >> 16);                              // ds_write_b8_d16_hi
-#else
-                                    d[0] = (uint8_t)c; d[1] = (uint8_t)(c >> 8); d[2] = (uint8_t)(c >> 16);
-#endif
-#endif
                                 }
                             }
                         }
@@ -1546,7 +1532,7 @@
             MGX_MARK("P5end");
         }
     }
-    }   // if !kPipe
+    }   // 3-byte staging
     }   // if !OH
     if constexpr (PERSIST) {
         // ------------------------------------------------------------ publish: every output store of this wavefront has left it

@@ -238,6 +238,43 @@ MGX_HD uint32_t agent_cell_raw(int cb, uint64_t row) { return cb == 1 ? agent_ce
 MGX_HD uint32_t load_obs_cell(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16); }
 MGX_HD void store_obs_cell(uint8_t *p, uint32_t c) { p[0] = (uint8_t)c; p[1] = (uint8_t)(c >> 8); p[2] = (uint8_t)(c >> 16); }
 
+// v_perm_b32 (__builtin_amdgcn_perm(hi, lo, sel)): byte i of the result = byte sel.i of the pair {hi, lo} -- 0-3 lo's bytes, 4-7 hi's,
+// 12 = 0x00 (the only other selector value used here).  The host form restates it for the CPU tests.
+MGX_HD uint32_t perm_b32(uint32_t hi, uint32_t lo, uint32_t sel) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_perm(hi, lo, sel);
+#else
+    const uint64_t pair = ((uint64_t)hi << 32) | lo;
+    uint32_t r = 0;
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t s = (sel >> (8 * i)) & 0xffu;
+        r |= (s < 8 ? (uint32_t)(pair >> (8 * s)) & 0xffu : (s == 12 ? 0u : 0xffu)) << (8 * i);
+    }
+    return r;
+#endif
+}
+// Dword staging of the observation (the one-step kernels, views of one lane pass; mgx_fused_body.inc P4/P5): every cell is staged
+// as one dword (type, color, state, junk), and P5 compacts 4 cells into 12 output bytes per lane.
+// Staging selector of P4: the 16-bit cells of two view slots share a register; tc = their (type, color) bytes (x & 0x070f070f),
+// st = their state in byte 0 of each half ((x >> 12) & 0x00030003); `hi`: the slot in the register's high half.
+MGX_HD constexpr uint32_t obs_stage_sel(bool hi) { return hi ? 0x0c060302u : 0x0c040100u; }
+// P5, stage 1: 4 staged cells d0..d3 -> their 12 packed bytes as 3 dwords, dword k = perm(d[k + 1], d[k], obs_pack_sel(k))
+MGX_HD constexpr uint32_t obs_pack_sel(int k) { return k == 0 ? 0x04020100u : (k == 1 ? 0x05040201u : 0x06050402u); }
+// P5, stage 2: the wavefront's bytes start s = o0 mod 4 bytes into a dword; the 12 bytes a lane stores (dword-aligned) are its
+// packed bytes moved up by s, the first s of them taken from the cell before (dm1 << 8: its bytes in bytes 1-3):
+// dword k = perm(packed k, packed k - 1, obs_shift_sel(s)); s = 0 leaves them as they are.
+MGX_HD constexpr uint32_t obs_shift_sel(int s) {
+    return (uint32_t)(4 - s) | ((uint32_t)(5 - s) << 8) | ((uint32_t)(6 - s) << 16) | ((uint32_t)(7 - s) << 24);
+}
+// The 12 bytes that start 12 u - s bytes into a run of packed cells, from its cells 4u - 1 .. 4u + 3 (staged dwords dm1, d0..d3;
+// dm1 is read only when s != 0).  Output bytes [12 u - s, 12 u - s + 12) of the run are w[0..2] in memory order.
+MGX_HD void obs_unit(uint32_t dm1, uint32_t d0, uint32_t d1, uint32_t d2, uint32_t d3, int s, uint32_t (&w)[3]) {
+    const uint32_t p0 = perm_b32(d1, d0, obs_pack_sel(0)), p1 = perm_b32(d2, d1, obs_pack_sel(1)), p2 = perm_b32(d3, d2, obs_pack_sel(2));
+    if (s == 0) { w[0] = p0; w[1] = p1; w[2] = p2; return; }
+    const uint32_t sel = obs_shift_sel(s);
+    w[0] = perm_b32(p0, dm1 << 8, sel); w[1] = perm_b32(p1, p0, sel); w[2] = perm_b32(p2, p1, sel);
+}
+
 // base.py:598-602 `1 - 0.9 * (step_count / max_steps)` in Python float arithmetic: three correctly rounded
 // IEEE-754 binary64 operations, never contracted into an fma (the library is built with -ffp-contract=off).
 MGX_HD double reward_value(int32_t step_count, int32_t max_steps) {
