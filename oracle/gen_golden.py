@@ -324,6 +324,7 @@ def main():
     record_custom(custom_envs.CASES_R6)
     record_custom_steps(custom_envs.STEP_CASES_R6)
     record_edge()            # (behind everything older for the same reason)
+    record_random_states()   # (constructs no registered env: every make_env() above keeps its construction seed)
 
 
 def face(env, i, target_xy, carrying=None):
@@ -684,6 +685,219 @@ def record_box_rollout():
     record("boxkey_a3", env, "empty", 9, T, None, script=script,
            note="BoxTreasureEnv (tests/custom_envs.py): boxes that hold a key / ball / goal / door / lava; agent 0 opens the key box, "
                 "takes the key and unlocks the purple door")
+
+
+#: product box-content kind (include/mgx.h "BOX CONTENTS") -> (Type index, state) of the object the box holds; the inverse of
+#: content_code (a door comes out of a box closed and unlocked)
+_CONTENT_CELL = {1: (5, 0), 2: (6, 0), 3: (8, 0), 4: (3, 0), 5: (9, 0), 6: (2, 0), 7: (4, 1)}
+
+#: The random-state corpus (tests/golden/randstate_*.npz): batches of tests.util.random_state -- stacked agents, terminated agents
+#: in the middle of the grid, agents on goals / lava, objects carried from the start, doors in every state, arbitrary PCG64 states
+#: and step counts up to max_steps - 1 -- each loaded into the REAL reference and stepped there.
+#: (name, EnvSpec keywords, batch, steps, random_state keywords)
+RANDSTATE_SPECS = [
+    ("randstate_7x5_a1_v3_see", dict(width=7, height=5, num_agents=1, view_size=3, max_steps=10, see_through_walls=True),
+     32, 16, dict(density=0.35, carry_p=0.5)),
+    ("randstate_9x6_a2_v5_noovl", dict(width=9, height=6, num_agents=2, view_size=5, max_steps=12, allow_agent_overlap=False),
+     48, 16, dict(density=0.3, terminated_p=0.3, carry_p=0.6)),
+    ("randstate_10x8_a3_v7_all_joint", dict(width=10, height=8, num_agents=3, view_size=7, max_steps=14, joint_reward=True,
+                                            success_termination_mode="all", failure_termination_mode="any"),
+     48, 16, dict(density=0.35, terminated_p=0.15)),
+    ("randstate_16x16_a4_v7", dict(width=16, height=16, num_agents=4, view_size=7, max_steps=20),
+     32, 12, dict(density=0.3, terminated_p=0.15, carry_p=0.4)),
+    ("randstate_13x10_a5_v9_noovl_any", dict(width=13, height=10, num_agents=5, view_size=9, max_steps=200, allow_agent_overlap=False,
+                                             success_termination_mode="all", failure_termination_mode="any"),
+     32, 14, dict(density=0.3, terminated_p=0.25, carry_p=0.5)),
+    ("randstate_12x15_a7_v11_joint", dict(width=12, height=15, num_agents=7, view_size=11, max_steps=30, joint_reward=True),
+     24, 12, dict(density=0.25, terminated_p=0.1)),
+    ("randstate_20x14_a16_v15_noovl", dict(width=20, height=14, num_agents=16, view_size=15, max_steps=65535,
+                                           allow_agent_overlap=False, failure_termination_mode="any"),
+     16, 10, dict(density=0.2, terminated_p=0.2, carry_p=0.5)),
+    ("randstate_10x9_a3_v7_boxes", dict(width=10, height=9, num_agents=3, view_size=7, max_steps=40),
+     48, 16, dict(density=0.4, carry_p=0.5, box_contents_p=0.7)),
+    ("randstate_10x8_a4_v5_edge", dict(width=10, height=8, num_agents=4, view_size=5, max_steps=30, allow_agent_overlap=False),
+     32, 12, dict(density=0.3, terminated_p=0.1, edge_agents=True)),
+    ("randstate_8x11_a2_v9_see_all", dict(width=8, height=11, num_agents=2, view_size=9, max_steps=1 << 20, see_through_walls=True,
+                                          success_termination_mode="all", joint_reward=True),
+     32, 14, dict(density=0.35, terminated_p=0.1, carry_p=0.4)),
+    ("randstate_bup_11x6_a2_v7", dict(width=11, height=6, num_agents=2, view_size=7, max_steps=16, joint_reward=True,
+                                      env_kind="blockedunlockpickup"),
+     32, 16, dict(density=0.3, carry_p=0.5)),
+    ("randstate_64x64_a16_v9", dict(width=64, height=64, num_agents=16, view_size=9, max_steps=4 * 64 * 64),
+     16, 6, dict(density=0.08, terminated_p=0.1)),
+]
+
+
+def _bup_target(st, b, r):
+    """BlockedUnlockPickup pays for carrying `env.obj` -- the one box object, by identity (envs/blockedunlockpickup.py:166-175,
+    world_object.py: WorldObj.__eq__) -- while the product compares the carried cell with the target's bytes (aux).  A random state
+    becomes a BlockedUnlockPickup state by keeping ONE box of the target's colour, in the grid or in an agent's hands, and giving the
+    others another colour.  Returns where the target is: ("grid", x, y), ("agent", i) or None (no box left to be it)."""
+    grid, agents = st["grid"][b], st["agents"][b]
+    boxes = [("grid", int(x), int(y)) for y, x in np.argwhere(grid[..., 0] == 7)] + \
+            [("agent", int(i)) for i in np.nonzero(agents[:, 5] == 7)[0]]
+    where = boxes[int(r.integers(len(boxes)))] if boxes and r.random() < 0.9 else None
+    if where is not None:
+        c = int(grid[where[2], where[1], 1]) if where[0] == "grid" else int(agents[where[1], 6])
+        st["target"][b, 1] = c
+    c = int(st["target"][b, 1])
+    for w in boxes:
+        if w == where:
+            continue
+        cell = grid[w[2], w[1]] if w[0] == "grid" else agents[w[1], 5:8]
+        if int(cell[1]) == c:
+            cell[1] = (c + 1 + int(r.integers(5))) % 6
+    return where
+
+
+def _grey_walls_in_boxes(st):
+    """Wall() is ONE cached instance in the reference (world_object.py:369-377: `functools.cache` on __new__), and
+    WorldObj.decode writes the colour into it -- so a wall a box holds has the colour of the last wall decoded anywhere.  The
+    reference's walls are grey; random_state's box contents give walls any colour: those are made grey here."""
+    for arr in (st["grid"], st["agents"][..., 5:8]):
+        code = arr[..., 2] >> 2
+        wall = (arr[..., 0] == 7) & ((code & 7) == 6)
+        arr[..., 2] = np.where(wall, (arr[..., 2] & 3) | ((6 | 5 << 3) << 2), arr[..., 2])
+
+
+def _decode(t, c, s):
+    """A product cell (type, color, state | content << 2) -> a reference WorldObj (or None), through WorldObj.decode."""
+    from multigrid.core.world_object import WorldObj
+    obj = WorldObj.decode(int(t), int(c), int(s) & 3 if t == 7 else int(s))
+    if t == 7 and int(s) >> 2:
+        code = int(s) >> 2
+        kind, state = _CONTENT_CELL[code & 7]
+        obj.contains = WorldObj.decode(kind, code >> 3, state)
+    return obj
+
+
+def _loaded_env(spec, st, b, target_at):
+    """A reference env holding env `b` of the product-layout state `st`: a subclass of MultiGridEnv (or BlockedUnlockPickupEnv)
+    whose _gen_grid -- the reference's extension point, base.py:229-247 -- builds Grid(W, H) with Grid.set and places the agents
+    through their AgentState fields."""
+    from multigrid.base import MultiGridEnv
+    from multigrid.core.grid import Grid
+    bup = spec["env_kind"] == "blockedunlockpickup"
+    W, H, A = spec["width"], spec["height"], spec["num_agents"]
+    grid, agents = st["grid"][b], st["agents"][b]
+
+    def gen_grid(self, width, height):
+        self.grid = Grid(width, height)
+        self.obj = None
+        for y in range(height):
+            for x in range(width):
+                t, c, s = (int(v) for v in grid[y, x])
+                if t != 1:
+                    obj = _decode(t, c, s)
+                    self.grid.set(x, y, obj)
+                    if target_at == ("grid", x, y):
+                        self.obj = obj
+        for agent in self.agents:
+            row = agents[agent.index]
+            agent.state.dir = int(row[1])
+            agent.state.pos = (int(row[2]), int(row[3]))
+            agent.state.terminated = bool(row[4])
+            agent.state.carrying = _decode(*row[5:8]) if row[5] != 1 else None
+            if target_at == ("agent", agent.index):
+                self.obj = agent.state.carrying
+        if bup and self.obj is None:                     # (the target box is nowhere: nothing can be paid for carrying it)
+            self.obj = _decode(7, int(st["target"][b, 1]), 0)
+
+    kw = dict(agents=A, max_steps=spec["max_steps"], agent_view_size=spec["view_size"], see_through_walls=spec["see_through_walls"],
+              allow_agent_overlap=spec["allow_agent_overlap"], joint_reward=spec["joint_reward"],
+              success_termination_mode=spec["success_termination_mode"], failure_termination_mode=spec["failure_termination_mode"])
+    if bup:
+        assert (W, H) == (11, 6)
+        base = ref_envs.BlockedUnlockPickupEnv
+        kw.pop("success_termination_mode")               # (BlockedUnlockPickupEnv fixes it to 'any')
+        cls = type("LoadedBlockedUnlockPickup", (base,), dict(_gen_grid=gen_grid))
+        env = cls(room_size=6, **kw)
+    else:
+        cls = type("LoadedState", (MultiGridEnv,), dict(_gen_grid=gen_grid))
+        env = cls(width=W, height=H, **kw)
+    env.reset(seed=0)
+    lo_s, hi_s, lo_i, hi_i = (int(w) for w in st["rng"][b])
+    bg = env.np_random.bit_generator
+    state = bg.state
+    state["state"] = {"state": lo_s | (hi_s << 64), "inc": lo_i | (hi_i << 64)}
+    state["has_uint32"], state["uinteger"] = 0, 0
+    bg.state = state
+    env.step_count = int(st["step_count"][b])
+    return env
+
+
+def _product_rng(gen) -> np.ndarray:
+    st = gen.bit_generator.state["state"]
+    s, inc = int(st["state"]), int(st["inc"])
+    return np.array([s & M64, s >> 64, inc & M64, inc >> 64], dtype=np.uint64)
+
+
+def record_random_states():
+    """Every spec of RANDSTATE_SPECS: a batch of tests.util.random_state envs, each loaded into the reference (_loaded_env) and
+    stepped T times with random actions (5 % of the keys missing).  Arrays, all in the PRODUCT layout, batch-major per step:
+
+        grid0 u8[B,H,W,3], agents0 u8[B,A,8], rng0 u64[B,4] ([state_lo, state_hi, inc_lo, inc_hi]), step_count0 i32[B], aux u8[B,16]
+        obs0 u8[B,A,v,v,3], dir0 u8[B,A]                   env.gen_obs() of the loaded state
+        actions i8[T,B,A]                                  -1 = the agent's key is absent from the dict
+        obs u8[T,B,A,v,v,3], dir u8[T,B,A], reward f64[T,B,A], terminated u8[T,B,A], truncated u8[T,B]
+        grid u8[T,B,H,W,3], agents u8[T,B,A,8], rng u64[T,B,4]   post-step state (box contents folded into the state bytes)
+        spec_json                                          EnvSpec.as_dict() of the spec (+ the random_state keywords)"""
+    sys.path.insert(0, REPO)
+    from multigrid_amd import layouts
+    from multigrid_amd.spec import EnvSpec
+    from tests import util
+    total = 0
+    for n, (fname, kw, B, T, rs_kw) in enumerate(RANDSTATE_SPECS):
+        spec = EnvSpec(**kw)
+        sd = spec.as_dict()
+        st = util.random_state(spec, B, seed=7000 + n, **rs_kw)
+        _grey_walls_in_boxes(st)
+        r = np.random.default_rng(8000 + n)
+        if spec.env_kind == "blockedunlockpickup":
+            targets = [_bup_target(st, b, r) for b in range(B)]
+        else:
+            targets = [None] * B
+            st["target"][:] = 0
+        # (forward-heavy, so that agents reach goals and lava, and run into each other)
+        actions = r.choice(7, size=(T, B, spec.num_agents), p=[0.12, 0.12, 0.4, 0.1, 0.1, 0.12, 0.04]).astype(np.int8)
+        actions[r.random(actions.shape) < 0.05] = -1
+        rec = dict(grid0=st["grid"], agents0=st["agents"], rng0=st["rng"], step_count0=st["step_count"], aux=st["target"],
+                   actions=actions)
+        keys = ("obs", "dir", "reward", "terminated", "truncated", "grid", "agents", "rng")
+        log = {k: [[None] * B for _ in range(T)] for k in keys}
+        obs0, dir0 = [], []
+        for b in range(B):
+            env = _loaded_env(sd, st, b, targets[b])
+            assert (layouts.grid_to_product(grid_with_contents(env)) == st["grid"][b]).all()
+            assert (layouts.pack_agents(agents_with_contents(env)) == st["agents"][b]).all()
+            o = env.gen_obs()
+            obs0.append(np.stack([o[i]["image"] for i in range(spec.num_agents)]))
+            dir0.append([int(o[i]["direction"]) for i in range(spec.num_agents)])
+            for t in range(T):
+                act = {i: int(a) for i, a in enumerate(actions[t, b]) if a >= 0}
+                o, rew, term, trunc, _ = env.step(act)
+                A = spec.num_agents
+                log["obs"][t][b] = np.stack([o[i]["image"] for i in range(A)])
+                log["dir"][t][b] = [int(o[i]["direction"]) for i in range(A)]
+                log["reward"][t][b] = [float(rew[i]) for i in range(A)]
+                log["terminated"][t][b] = [bool(term[i]) for i in range(A)]
+                log["truncated"][t][b] = bool(trunc[0])
+                log["grid"][t][b] = layouts.grid_to_product(grid_with_contents(env))
+                log["agents"][t][b] = layouts.pack_agents(agents_with_contents(env))
+                log["rng"][t][b] = _product_rng(env.np_random)
+        rec["obs0"] = np.asarray(obs0).astype(np.uint8)
+        rec["dir0"] = np.asarray(dir0).astype(np.uint8)
+        for k in keys:
+            arr = np.asarray(log[k])
+            rec[k] = arr.astype(np.float64) if k == "reward" else arr if k == "rng" else arr.astype(np.uint8)
+        rec["spec_json"] = np.array(json.dumps(dict(sd, random_state=rs_kw, seed=7000 + n)))
+        path = os.path.join(OUT, fname + ".npz")
+        np.savez_compressed(path, **rec)
+        total += os.path.getsize(path)
+        print(f"{fname:34s} B={B:3d} T={T:3d} success-steps={int((rec['reward'] > 0).any(axis=2).sum()):4d} "
+              f"truncated={int(rec['truncated'].sum()):4d} {os.path.getsize(path) / 1024:.1f} KiB")
+    print(f"random-state corpus: {total / 1024:.1f} KiB")
+    assert total <= 1 << 20, "the random-state corpus must stay within 1 MiB"
 
 
 def spec_of_noreset(env, kind):

@@ -154,3 +154,30 @@ def test_pcg64_advance_equals_that_many_numpy_draws():
             g.random(n * k)
         st = g.bit_generator.state["state"]
         assert (int(w[0]), int(w[1]), int(w[2]), int(w[3])) == (st["state"] & m, st["state"] >> 64, st["inc"] & m, st["inc"] >> 64), (seed, k, n)
+
+
+@pytest.mark.parametrize("force_serial", [False, True], ids=["fastpath", "serial"])
+@pytest.mark.parametrize("path", util.RANDSTATE_GOLDEN, ids=util.RANDSTATE_IDS)
+def test_rules_replay_reference_random_states(path, force_serial):
+    """The g++ build of mgx_rules.h, env by env, against the reference's own bytes on the random-state corpus
+    (tests/golden/randstate_*.npz): every output, the post-step grid, agents, generator words and step count, every step."""
+    z, d, spec = util.load_golden(path)
+    B, T = z["grid0"].shape[0], z["actions"].shape[0]
+    assert spec.env_kind in ("empty", "blockedunlockpickup")
+    for b in range(B):
+        tile, rows = z["grid0"][b].copy(), z["agents0"][b].copy()
+        rng, sc, aux = z["rng0"][b].copy(), int(z["step_count0"][b]), z["aux"][b].copy()
+        np.testing.assert_array_equal(hostshim.obs_env(spec, tile, rows), z["obs0"][b])
+        for t in range(T):
+            out = hostshim.step_env(spec, tile, rows, np.ascontiguousarray(z["actions"][t, b]), rng, sc, aux, force_serial)
+            ctx = f"env {b} step {t}"
+            assert out["rc"] == 0, ctx
+            sc = out["step_count"]
+            assert sc == int(z["step_count0"][b]) + t + 1, ctx
+            np.testing.assert_array_equal(out["obs"], z["obs"][t, b], err_msg=ctx)
+            assert out["reward"].tobytes() == z["reward"][t, b].tobytes(), ctx
+            np.testing.assert_array_equal(out["terminated"], z["terminated"][t, b], err_msg=ctx)
+            assert out["truncated"] == int(z["truncated"][t, b]), ctx
+            np.testing.assert_array_equal(tile, z["grid"][t, b], err_msg=ctx)
+            np.testing.assert_array_equal(rows, z["agents"][t, b], err_msg=ctx)
+            np.testing.assert_array_equal(rng, z["rng"][t, b], err_msg=ctx)

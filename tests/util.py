@@ -15,7 +15,7 @@ from oracle import binding as ob
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 _ALL = sorted(glob.glob(os.path.join(GOLDEN_DIR, "*.npz")))
 #: rollout fixtures (state + actions + per-step outputs) and reset/layout fixtures, both written by oracle/gen_golden.py
-GOLDEN = [p for p in _ALL if not os.path.basename(p).startswith(("layout_", "wrappers_", "custom_", "customsteps_"))]
+GOLDEN = [p for p in _ALL if not os.path.basename(p).startswith(("layout_", "wrappers_", "custom_", "customsteps_", "randstate_"))]
 GOLDEN_IDS = [os.path.basename(p)[:-4] for p in GOLDEN]
 LAYOUT_GOLDEN = [p for p in _ALL if os.path.basename(p).startswith("layout_")]
 LAYOUT_IDS = [os.path.basename(p)[:-4] for p in LAYOUT_GOLDEN]
@@ -30,6 +30,10 @@ CUSTOM_IDS = [os.path.basename(p)[:-4] for p in CUSTOM_GOLDEN]
 #: (oracle/gen_golden.py: record_custom_steps)
 CUSTOM_STEPS_GOLDEN = [p for p in _ALL if os.path.basename(p).startswith("customsteps_")]
 CUSTOM_STEPS_IDS = [os.path.basename(p)[:-4] for p in CUSTOM_STEPS_GOLDEN]
+#: batches of `random_state` envs loaded into the reference and stepped there, product layout, batch-major per step
+#: (oracle/gen_golden.py: record_random_states)
+RANDSTATE_GOLDEN = [p for p in _ALL if os.path.basename(p).startswith("randstate_")]
+RANDSTATE_IDS = [os.path.basename(p)[:-4] for p in RANDSTATE_GOLDEN]
 WRAPPER_GOLDEN = [p for p in _ALL if os.path.basename(p).startswith("wrappers_")]
 WRAPPER_IDS = [os.path.basename(p)[:-4] for p in WRAPPER_GOLDEN]
 
