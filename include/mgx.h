@@ -597,6 +597,23 @@ int mgx_persistent_wait(const uint32_t *done, int32_t waves, uint32_t step, uint
 int mgx_persistent_feed(const MgxSpec *spec, int64_t batch, const int8_t *actions, int32_t steps, const MgxPersistent *p,
                         int32_t waves, uint64_t *trace, void *stream);
 
+/* RGB FRAMES (additive to ABI 11): MultiGridEnv.get_full_render (multigrid/base.py:707-760), the frame the reference's get_frame()
+ * and render_mode="rgb_array" return.  A frame is a grid of tiles and a tile depends only on a key -- the cell's appearance (50:
+ * empty, lava, 18 doors, 6 colours each of wall / goal, floor, key, ball, box; a box draws the same whatever it holds), the agent
+ * drawn over it (none, or 6 colours x 4 directions) and whether it is highlighted -- so the 2 500 tiles are rendered once per tile
+ * size into an ATLAS, bit for bit as Grid.render_tile draws them with its cache off (multigrid/core/grid.py:198-254; csrc/mgx_render.h),
+ * and the frames are assembled from atlas rows.
+ *   mgx_render_atlas  atlas u8[2500, tile_size, tile_size, 3]; tile_size 1..64.
+ *   mgx_render        frames u8[n, H*tile_size, W*tile_size, 3] (the reference's frame layout) of the n envs grid / agents, in any
+ *                     cell format of spec->cell_bytes.  The agent drawn on a cell is the highest-index NON-terminated agent there
+ *                     (grid.py:281-283); a cell with terminated agents only shows none.  obs (may be NULL = no highlight) is the
+ *                     mgx_gen_obs observation of the same state, u8[n, A, v, v, 3]: a cell is highlighted when it is visible
+ *                     (type != unseen) in the view of any agent, terminated or not (base.py:712-747).
+ * tile_size outside 1..64, or a NULL pointer with n > 0: MGX_ERR_INVALID_ARGUMENT.  Neither function synchronises. */
+int mgx_render_atlas(int32_t tile_size, uint8_t *atlas, void *stream);
+int mgx_render(const MgxSpec *spec, int64_t n, const MgxCell *grid, const uint8_t *agents, const uint8_t *obs, const uint8_t *atlas,
+               int32_t tile_size, uint8_t *frames, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,7 +28,7 @@ EXPORTS = ("mgx_abi_version", "mgx_error_string", "mgx_last_hip_error", "mgx_gen
            "mgx_step_ex", "mgx_step_chains", "mgx_sub_shards",
            "mgx_pack_grid_env", "mgx_check_grid", "mgx_pack_grid8_env", "mgx_unpack_grid8", "mgx_shape_key", "mgx_shape_register", "mgx_stage_generate",
            "mgx_persistent_waves", "mgx_step_persistent", "mgx_persistent_post", "mgx_persistent_wait", "mgx_persistent_feed",
-           "mgx_rollout_info")
+           "mgx_rollout_info", "mgx_render_atlas", "mgx_render")
 
 
 class MgxLaunchInfo(C.Structure):
@@ -162,6 +162,10 @@ def lib() -> C.CDLL:
     L.mgx_persistent_wait.argtypes = [vp, C.c_int32, C.c_uint32, vp, C.c_int32, vp]
     L.mgx_persistent_feed.restype = C.c_int
     L.mgx_persistent_feed.argtypes = [C.POINTER(MgxSpecC), i64, vp, C.c_int32, C.POINTER(MgxPersistent), C.c_int32, vp, vp]
+    L.mgx_render_atlas.restype = C.c_int
+    L.mgx_render_atlas.argtypes = [C.c_int32, vp, vp]
+    L.mgx_render.restype = C.c_int
+    L.mgx_render.argtypes = [C.POINTER(MgxSpecC), i64, vp, vp, vp, vp, C.c_int32, vp, vp]
     if L.mgx_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH}: ABI version {L.mgx_abi_version()} != {ABI_VERSION}; rebuild it")
     _lib = L

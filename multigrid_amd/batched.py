@@ -706,6 +706,51 @@ class BatchedMultiGridEnv:
             self._full.copy_(img)
         return self._full
 
+    def render(self, env_ids=None, tile_size: int = 32, highlight: bool = True, out: torch.Tensor | None = None) -> torch.Tensor:
+        """RGB frames, u8[N, H*tile_size, W*tile_size, 3] on the device: `MultiGridEnv.get_full_render(highlight, tile_size)`
+        (multigrid/base.py:707-760) of every env, or of the envs `env_ids` (an integer tensor, e.g. a few envs of a big batch to
+        log).  `highlight` shades the cells any agent sees, from a gen_obs of the state into a private buffer: the env's state and
+        every buffer it has handed out (obs, dir, one-hot, reward, the flags) are left as they are.  `out`: a contiguous uint8
+        tensor of that shape on this device to write into.  Tiles come from an atlas rendered once per (device, tile_size)."""
+        self._no_session("render")
+        self._need_state()
+        self.join()
+        ts = int(tile_size)
+        if not 1 <= ts <= 64:
+            raise ValueError(f"render: tile_size must be in 1..64, got {tile_size}")
+        cells, agents = self.cells, self.agents
+        if env_ids is not None:
+            ids = torch.as_tensor(env_ids)
+            if ids.dtype.is_floating_point or ids.dtype.is_complex or ids.dtype == torch.bool:
+                raise TypeError(f"render: env_ids must be an integer tensor, got {ids.dtype}")
+            if ids.dim() != 1:
+                raise ValueError(f"render: env_ids must be one-dimensional, got shape {tuple(ids.shape)}")
+            if ids.numel():
+                lo, hi = (int(v) for v in torch.stack((ids.min(), ids.max())).tolist())
+                if lo < 0 or hi >= self.batch:
+                    raise ValueError(f"render: env_ids must lie in [0, {self.batch}), got {lo}..{hi}")
+            ids = ids.to(device=self.device, dtype=torch.long)
+            cells, agents = cells.index_select(0, ids), agents.index_select(0, ids)
+        n, sp = cells.shape[0], self.spec
+        shape = (n, sp.height * ts, sp.width * ts, 3)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        elif (tuple(out.shape) != shape or out.dtype != torch.uint8 or out.device != self.device or not out.is_contiguous()):
+            raise ValueError(f"render: out must be a contiguous uint8 tensor of shape {shape} on {self.device}")
+        if n == 0:
+            return out
+        obs = None
+        if highlight:
+            scratch = getattr(self, "_render_scratch", None)
+            if scratch is None or scratch[0].shape[0] < n:
+                scratch = (torch.empty((n,) + tuple(self.obs.shape[1:]), dtype=torch.uint8, device=self.device),
+                           torch.empty((n, sp.num_agents), dtype=torch.uint8, device=self.device))
+                self._render_scratch = scratch
+            obs, dirs = scratch[0][:n], scratch[1][:n]
+            self.backend.gen_obs(n, cells, agents, obs, dirs)
+        self.backend.render(n, cells, agents, obs, ts, out)
+        return out
+
     def set_layout_pool(self, grids, agents, auxs=None):
         """Pool of K pre-generated episode starts for `reset_done()`: u8[K,H,W,3], u8[K,A,8], u8[K,16] | None."""
         self._no_session("set_layout_pool")

@@ -27,11 +27,11 @@ VIEWS = (3, 5, 7, 9, 11, 13, 15)
 #: translation units: (object name, source, extra defines).  The fused kernel is instantiated in one unit per view size so
 #: that the units compile in parallel (a single unit took a minute).
 UNITS = ([("mgx_kernels", os.path.join(CSRC, "mgx_kernels.hip"), ()), ("mgx_aux", os.path.join(CSRC, "mgx_aux.hip"), ()),
-          ("mgx_layout_gen", os.path.join(CSRC, "mgx_layout_gen.hip"), ())]
+          ("mgx_layout_gen", os.path.join(CSRC, "mgx_layout_gen.hip"), ()), ("mgx_render", os.path.join(CSRC, "mgx_render.hip"), ())]
          + [(f"mgx_fused_v{v}", os.path.join(CSRC, "mgx_fused_inst.hip"), (f"MGX_INST_V={v}",)) for v in VIEWS])
 SRCS = sorted({u[1] for u in UNITS})
 DEPS = SRCS + [os.path.join(CSRC, "mgx_fused.h"), os.path.join(CSRC, "mgx_fused_body.inc"), os.path.join(CSRC, "mgx_layout_gen.h"), os.path.join(CSRC, "mgx_rules.h"),
-               os.path.join(ROOT, "include", "mgx.h")]
+               os.path.join(CSRC, "mgx_render.h"), os.path.join(ROOT, "include", "mgx.h")]
 LIB = os.path.join(HERE, "lib", "libmgx.so")
 LIB_DBG = os.path.join(HERE, "lib", "libmgx_dbg.so")
 LIB_CHK = os.path.join(HERE, "lib", "libmgx_chk.so")

@@ -20,7 +20,9 @@ User-defined envs.  Both of the reference's extension points run unchanged:
     very object that was put there (matched by what the device cell holds), so the reference's `==` (identity,
     world_object.py:126-127) means the same here.
 
-Out of scope: `render()` and everything pygame, user-defined object types.
+Rendering: `get_frame()` / `get_full_render()` and `render_mode="rgb_array"` + `render()` return the reference's RGB frame
+(base.py:707-833), rendered on the device (`BatchedMultiGridEnv.render`).  Out of scope: `"human"` mode and
+everything pygame, agent-POV rendering (the reference raises for it too), user-defined object types.
 """
 from __future__ import annotations
 
@@ -295,8 +297,8 @@ class MultiGridEnv:
     (multigrid/base.py:229-247; see the module docstring) -- or as `_gen_layout` (ready-made product tensors: what the
     built-in env classes do), and may override `step` the reference's way (module docstring)."""
 
-    metadata = {"render_modes": [], "render_fps": 20}
-    render_mode = None                   # (rendering is out of scope: the constructor refuses any other value)
+    metadata = {"render_modes": ["rgb_array"], "render_fps": 20}
+    render_mode = None                   # None or "rgb_array" ("human" needs a display and pygame: refused)
     env_kind = "empty"
 
     def __init__(
@@ -317,12 +319,15 @@ class MultiGridEnv:
             device="cuda",
             layout_seed: int | None = None,
             _backend=None,
+            highlight: bool = True,
+            tile_size: int = 32,
             **unused_render_kwargs: Any):
         """Keyword arguments as multigrid/base.py:85-103.  Extras: `device` (HIP device), `layout_seed` (seed of
         the construction-time generator that drives object placement -- the reference takes it from OS
-        entropy)."""
-        if render_mode is not None:
-            raise NotImplementedError("rendering is out of scope for multigrid_amd (SURVEY.md section 2)")
+        entropy).  `render_mode` None or "rgb_array"; `highlight` / `tile_size` are what `render()` passes to
+        `get_frame` (base.py:100-103); the reference's other display keywords (screen_size, agent_pov) are accepted and unused."""
+        if render_mode not in (None, "rgb_array"):
+            raise NotImplementedError(f"render_mode {render_mode!r}: multigrid_amd renders 'rgb_array' frames only (no display)")
         self._gen_agents: np.ndarray | None = None        # (A,9) initial agent rows while a user's _gen_grid runs
         self._gen_carry_content: dict = {}                # ... and the contents of boxes it hands to agents
         self._objects_at: dict = {}                       # (x, y) -> the WorldObj known to lie there (identity of placed objects)
@@ -356,7 +361,8 @@ class MultiGridEnv:
         self.joint_reward = joint_reward
         self.success_termination_mode = success_termination_mode
         self.failure_termination_mode = failure_termination_mode
-        self.render_mode = None
+        self.render_mode = render_mode
+        self.highlight, self.tile_size = highlight, tile_size
         self.actions = Action
         self.reward_range = (0, 1)
         if given_agents is None:
@@ -824,8 +830,26 @@ class MultiGridEnv:
         """multigrid/base.py:534-539"""
         return bool(self._benv.is_done()[0])
 
+    def get_pov_render(self, *args, **kwargs):
+        """base.py:699-705"""
+        raise NotImplementedError("POV rendering not supported for multiagent environments.")
+
+    def get_full_render(self, highlight: bool, tile_size: int) -> np.ndarray:
+        """base.py:707-760: the whole grid, uint8 (H*tile_size, W*tile_size, 3), the cells the agents see highlighted."""
+        return self._benv.render(None, tile_size, highlight)[0].cpu().numpy()
+
+    def get_frame(self, highlight: bool = True, tile_size: int = 32, agent_pov: bool = False) -> np.ndarray:
+        """base.py:762-789"""
+        if agent_pov:
+            return self.get_pov_render(tile_size)
+        return self.get_full_render(highlight, tile_size)
+
     def render(self):
-        raise NotImplementedError("rendering is out of scope for multigrid_amd (SURVEY.md section 2)")
+        """base.py:791-833, "rgb_array" mode: the frame.  Without a render mode there is nothing to render to (the reference
+        returns None there; this raises, as before rendering existed)."""
+        if self.render_mode != "rgb_array":
+            raise NotImplementedError("render() needs render_mode='rgb_array' (multigrid_amd has no display: no 'human' mode)")
+        return self.get_frame(self.highlight, self.tile_size)
 
     def close(self):
         pass

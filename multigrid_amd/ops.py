@@ -79,6 +79,10 @@ def _ptr(t):
     return t.data_ptr() if t is not None else None
 
 
+#: include/mgx.h mgx_render_atlas: 50 appearances x 25 agent overlays x highlight; tile sizes 1..64
+RENDER_KEYS, RENDER_MAX_TILE = 2500, 64
+_ATLASES: dict = {}            # (device index, tile_size) -> the atlas tensor
+
 ONE_HOT_DIMS = (11, 6, 4)      # len(Type), len(Color), max(len(State), len(Direction))  (multigrid/wrappers.py:139-140)
 
 
@@ -396,6 +400,28 @@ class HipBackend:
 
     def full_obs(self, B, grid, agents, out):
         _full_obs_into(self.sc, B, grid, agents, out)
+
+    def render_atlas(self, tile_size: int) -> torch.Tensor:
+        """u8[2500, ts, ts, 3]: every tile the reference can draw at this size (include/mgx.h mgx_render_atlas), cached per
+        (device, tile_size)."""
+        key = (self.device.index if self.device.index is not None else torch.cuda.current_device(), int(tile_size))
+        atlas = _ATLASES.get(key)
+        if atlas is None:
+            if not 1 <= int(tile_size) <= RENDER_MAX_TILE:
+                raise ValueError(f"tile_size must be in 1..{RENDER_MAX_TILE}, got {tile_size}")
+            atlas = torch.empty((RENDER_KEYS, tile_size, tile_size, 3), dtype=torch.uint8, device=self.device)
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().mgx_render_atlas(int(tile_size), atlas.data_ptr(), _stream(self.device)), "mgx_render_atlas")
+            _ATLASES[key] = atlas
+        return atlas
+
+    def render(self, n, grid, agents, obs, tile_size, frames):
+        """frames u8[n, H*ts, W*ts, 3] of the n envs `grid` / `agents`; `obs` = their gen_obs observation (highlight) or None."""
+        atlas = self.render_atlas(tile_size)
+        with torch.cuda.device(grid.device):
+            rc = _lib.lib().mgx_render(C.byref(self.sc), n, grid.data_ptr(), agents.data_ptr(), _ptr(obs), atlas.data_ptr(),
+                                       int(tile_size), frames.data_ptr(), _stream(grid.device))
+        _lib.check(rc, "mgx_render")
 
     def reset_done(self, B, first_env, pool, grid, agents, step_count, target, episode, was_reset):
         pg, pa, pt = pool
