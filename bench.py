@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the fused HIP step (action apply + gen_obs) on synthetic random-action rollouts.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c2|c3|c5] [--mode graph|eager]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c2|c3|c5] [--mode graph|eager] [--full]
+
+A plain run does only what its headline needs: set up, warm up, time the K steps, write --dump-outputs, print the line.  Every
+other point (the pipelined variant, the other scaling point, the other configurations, the CPU baselines, the per-kernel and
+HBM-resident rooflines: everything that takes runs of its own) is measured with --full.
 
 One "step" = one `MultiGridEnv.step` over the whole per-GPU batch = one launch of the fused kernel (auto-reset fused in).
 Headline workload = BASELINE.json's north-star configuration C4: MultiGrid-Empty-16x16-v0, agents=4, view_size=7,
@@ -10,31 +14,33 @@ batch=65536 envs -- all of it on one GPU at N=1 (it is ~100 MB).  For N>1 (launc
 the configuration's batch is SPLIT over the ranks (`--scaling strong`, the default since round 5: BASELINE.json configs[3] read
 literally -- 65536 envs sharded across the GPUs, 8192 per GPU at N=8, the shape the north star's 1e8 agent-steps/s target is stated
 on; rank r owns the global envs [r x 65536/N, (r+1) x 65536/N) -- seeds and synthetic state are functions of the global env
-index), and the SAME run then measures the weak point -- the configuration's batch on EVERY GPU, global batch N x 65536, flat by
-construction -- and carries it in the line as `weak` (`--scaling weak` makes that the headline and carries the split as
-`strong`).  The data path has NO collective -- envs never interact (SURVEY.md section
+index), and with --full the SAME run then measures the weak point -- the configuration's batch on EVERY GPU, global batch N x
+65536, flat by construction -- and carries it in the line as `weak` (`--scaling weak` makes that the headline and carries the
+split as `strong`).  The data path has NO collective -- envs never interact (SURVEY.md section
 8e) -- and torch.distributed (RCCL) is used only for the barrier and the max-over-ranks time.
 
 Timing.  W untimed warm-up steps, one untimed replay of each captured graph, then the timed region: exactly K steps, as
 K // c replays of a c-step hipGraph (c = min(K, 256)) and one of a (K % c)-step one; `ms_per_step` = region / K (choose K
 so that the region is long enough to time: ~20 us per step of C4).  The region is bracketed by barrier +
-torch.cuda.synchronize() on both sides, max over ranks.  The other points of the line (pipelined, weak / strong, configs)
+torch.cuda.synchronize() on both sides, max over ranks.  The other points of a --full line (pipelined, weak / strong, configs)
 replay whole blocks until their own region is >= 20-50 ms.
 --dump-outputs DIR writes what the headline's last timed step returned (see dump_outputs); the inputs are seeded, so two
 runs with the same arguments step the same envs with the same actions.
 
 `value` is the LOCK-STEP path: one launch of the fused kernel per step of the whole per-GPU batch, step t+1 enqueued behind step
-t (what a policy that needs all B observations of step t before step t+1 gets; the reference's own semantics).  Beside it,
+t (what a policy that needs all B observations of step t before step t+1 gets; the reference's own semantics).  Beside it (--full),
 `pipelined`: the same steps issued as independent chains of sub-shard launches (BatchedMultiGridEnv.capture_steps(sub_shards=
 "auto"), the product's own policy: mgx_sub_shards) -- valid for open-loop actions or a double-buffered actor loop.
 
-Prints ONE JSON line on rank 0.  Extra objects (N=1 only, except `roofline`, `pipelined` and -- N>1 -- `weak` / `strong`):
-  weak / strong       (N>1) the scaling point that is NOT the headline, measured in the same run: value, ms_per_step, per-rank
-                      min / max, roofline of that launch (`weak` beside the default strong headline)
+Prints ONE JSON line on rank 0.  Beside the headline fields and `config`, a plain run carries
   roofline            the fused kernel on the timed workload, by the literal definition: algorithmic bytes per launch (SURVEY.md
                       8d) / average launch duration from HIP events over the timed region on the launch stream (one launch per
                       step, back to back; rocprofv3's average for the kernel: profiles/); `traffic` = HBM bytes per launch from the
-                      committed rocprofv3 PMC passes (profiles/traffic.json)
+                      committed rocprofv3 PMC passes (profiles/traffic.json).  With --sub-shards P > 1 a plain run carries only
+                      `step_frac` here: the per-launch figure times one sub-shard launch alone, a run of its own (--full)
+--full adds (N=1 only, except `pipelined` and -- N>1 -- `weak` / `strong`):
+  weak / strong       (N>1) the scaling point that is NOT the headline, measured in the same run: value, ms_per_step, per-rank
+                      min / max, roofline of that launch (`weak` beside the default strong headline)
   pipelined           the sub-sharded variant: value, ms_per_step, `step_frac` (the step's bytes / the step's time: an aggregate over
                       several launches in flight) and `launch` (ONE sub-shard launch over its own duration: the literal per-launch
                       fraction); the overlap itself is shown by in-kernel timestamps in profiles/r3_chain_overlap.txt
@@ -767,19 +773,24 @@ def main():
     ap.add_argument("--no-auto-reset", action="store_true", help="step finished envs on as the reference does (base.py:408-409)")
     ap.add_argument("--sub-shards", type=int, default=1,
                     help="graph mode: the chains the HEADLINE steps the batch as (default 1: lock-step, one launch per step; 0 = "
-                         "the product's policy, BatchedMultiGridEnv.sub_shards_hint).  The pipelined variant is reported "
-                         "beside the headline either way")
+                         "the product's policy, BatchedMultiGridEnv.sub_shards_hint).  With --full the pipelined variant is "
+                         "reported beside a lock-step headline")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="strong",
                     help="N > 1: strong (default) = the configuration's batch split over the N GPUs (BASELINE.json configs[3] read "
                          "literally: 65 536 envs over 8 GPUs, the shape the 1e8 agent-steps/s target is stated on); weak = every "
                          "GPU steps the configuration's batch (per-GPU work fixed, the global batch grows with N; envs are "
-                         "independent, no collective).  The run also measures the OTHER point and carries it in the line as "
-                         "`weak` / `strong`")
-    ap.add_argument("--large-batch", type=int, default=1 << 20)
-    ap.add_argument("--no-extras", action="store_true", help="only the headline measurement + its roofline")
+                         "independent, no collective).  With --full the run also measures the OTHER point and carries it in the "
+                         "line as `weak` / `strong`")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline as well: the pipelined variant, the other scaling point (N > 1), "
+                         "the other configurations, eager / rollout / persistent / closed-loop points, the HBM-resident kernels and "
+                         "the CPU baselines (N = 1).  Without it the run times the headline alone")
+    ap.add_argument("--large-batch", type=int, default=1 << 20, help="--full: the batch of the HBM-resident kernel points")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="--full: only the points measured beside the headline (pipelined, weak / strong), not the N = 1 extras")
     ap.add_argument("--no-pipelined", action="store_true",
-                    help="skip the sub-sharded variant beside the headline (profiling: its launches are instances of the same kernel "
-                         "at half the batch and would mix into the kernel's rocprofv3 statistics)")
+                    help="--full: skip the sub-sharded variant beside the headline (profiling: its launches are instances of the same "
+                         "kernel at half the batch and would mix into the kernel's rocprofv3 statistics)")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write what the last of them returned (obs -- a seeded sample of the envs --, dir, "
                          "reward, terminated, truncated) as DIR/<name>.npy, float32 / float64; --gpus 1 only")
@@ -879,17 +890,17 @@ def main():
     if rank == 0:
         if P == 1:
             out["roofline"] = step_roofline(name, spec, B, m["event_ms"] / S)
-        else:                                                   # (--sub-shards: the literal per-launch number stays the `frac`)
-            out["roofline"] = step_roofline(name, spec, B // P, sub_shard_launch_ms(env, P, device))
+        else:       # (--sub-shards: the literal per-launch number stays the `frac`; it times a sub-shard launch alone: --full)
+            out["roofline"] = step_roofline(name, spec, B // P, sub_shard_launch_ms(env, P, device)) if args.full else {}
             out["roofline"]["step_frac"] = round(B * A * spec.bytes_step() / (m["event_ms"] / S * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
-    if P == 1 and hint > 1 and args.mode == "graph" and not args.no_pipelined:   # the pipelined variant beside the lock-step headline (all ranks)
+    if args.full and P == 1 and hint > 1 and args.mode == "graph" and not args.no_pipelined:   # beside the lock-step headline (all ranks)
         m2, pp = pipelined_point(name, spec, env, args.steps, device, barrier, 99 + rank, hint, min_region_ms=25.0,
                                  agree=lambda n: int(all_max(float(n))))
         pp["value"] = round(G * A * m2["timed_steps"] / all_max(m2["wall_s"]))
         if rank == 0:
             out["pipelined"] = pp
-    if world > 1:               # the OTHER scaling point of the same configuration, same run (all ranks): `weak` beside a strong
-                                # headline (the default), `strong` beside a weak one
+    if args.full and world > 1:  # the OTHER scaling point of the same configuration, same run (all ranks): `weak` beside a strong
+                                 # headline (the default), `strong` beside a weak one
         other = "weak" if args.scaling == "strong" else "strong"
         Go = G0 * world if other == "weak" else G0
         f2, B2 = shard_range(Go, rank, world)
@@ -914,9 +925,9 @@ def main():
     if rank == 0:
         out["roofline"]["cache_resident"] = bool(B * A * spec.bytes_step() < 200e6)
         if B * A * spec.bytes_step() < 200e6:
-            out["roofline"]["note"] = ("working set fits the 256 MiB Infinity Cache at this batch: see roofline_large for "
-                                       "the HBM-resident regime")
-        if not args.no_extras and world == 1:                  # everything else: N=1 only
+            out["roofline"]["note"] = ("working set fits the 256 MiB Infinity Cache at this batch: see roofline_large "
+                                       "(--full) for the HBM-resident regime")
+        if args.full and not args.no_extras and world == 1:    # everything else: N=1 only
             del env
             torch.cuda.empty_cache()
             out["configs"] = {c: config_point(c, device, 256, 50) for c in ("c2", "c3", "c5") if c != name}

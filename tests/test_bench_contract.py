@@ -3,6 +3,7 @@ import json
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 
@@ -10,13 +11,25 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 
 
-def test_bench_prints_the_contract_line():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "40", "--warmup", "5",
-                          "--no-extras"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+#: what a --full line carries beside the headline (N = 1)
+FULL_KEYS = {"pipelined", "configs", "eager", "fused_rollout", "fused_rollout_c4", "roofline_large", "gen_obs_large", "one_hot_large",
+             "aux_kernels", "device_generation", "persistent", "byte_grid_overhead", "closed_loop", "cpu_baseline",
+             "cpu_baseline_1core", "cpu_baseline_python_1core"}
+
+
+def _bench_line(*extra):
+    """Run `bench.py --gpus 1 --steps 40 --warmup 5 [extra]`; returns (its one JSON line, the run's wall seconds)."""
+    t0 = time.perf_counter()
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "40", "--warmup", "5", *extra],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    wall = time.perf_counter() - t0
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout
-    d = json.loads(lines[0])
+    return json.loads(lines[0]), wall
+
+
+def _check_headline(d):
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline"):
         assert k in d, k
@@ -35,10 +48,28 @@ def test_bench_prints_the_contract_line():
         assert k in r, k
     assert r["bound"] == "hbm" and r["peak"] == 8000.0 and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-3
     # the headline is the lock-step path -- ONE launch of the whole batch per step -- so `roofline.frac` is the literal
-    # per-launch number a kernel trace reproduces; the sub-sharded (pipelined) variant is carried beside it with its own
+    # per-launch number a kernel trace reproduces; --full carries the sub-sharded (pipelined) variant beside it with its own
     # per-launch fraction and the aggregate over the step
     assert d["config"]["sub_shards"] == 1 and r["algorithmic_bytes"] == 65536 * 4 * 339
     assert abs(r["ms_per_launch"] - d["ms_per_step"]) / d["ms_per_step"] < 0.1
+
+
+def test_bench_prints_the_contract_line():
+    """The plain run times the headline and nothing else: what --full adds is absent, and the run spends well under 30 s
+    outside its warm-up and timed steps."""
+    d, wall = _bench_line()
+    _check_headline(d)
+    assert not FULL_KEYS & set(d), FULL_KEYS & set(d)
+    assert wall - (40 + 5) * d["ms_per_step"] / 1e3 < 30, wall
+
+
+def test_bench_full_carries_every_other_point():
+    """--full: the same headline, and beside it the pipelined variant, the other configurations, the HBM-resident kernels and
+    the CPU baselines."""
+    d, _ = _bench_line("--full")
+    _check_headline(d)
+    assert FULL_KEYS <= set(d), FULL_KEYS - set(d)
+    assert {"c1", "c2", "c3", "c5"} <= set(d["configs"]) and d["roofline"]["hbm_resident"]["batch"] == 1 << 20
     p = d["pipelined"]
     assert p["sub_shards"] == 2 and p["launch"]["batch"] * 2 == 65536          # (mgx_sub_shards' answer: two chains, round 5)
     assert p["value"] > d["value"] * 0.9 and p["launch"]["frac"] < p["step_frac"]

@@ -62,8 +62,8 @@ def test_hip_ranks_equal_single_process(tmp_path, name, G, T, N):
 
 def test_bench_under_two_ranks_prints_the_strong_line_by_default():
     """The default for N > 1 (round 5): BASELINE.json configs[3] read literally -- the configuration's 65 536 envs SPLIT over the
-    ranks -- is `value`; the weak point (the configuration's batch on every GPU) rides along as `weak`."""
-    out = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5"])
+    ranks -- is `value`; with --full the weak point (the configuration's batch on every GPU) rides along as `weak`."""
+    out = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--full"])
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout
@@ -81,8 +81,9 @@ def test_bench_under_two_ranks_prints_the_strong_line_by_default():
 
 def test_bench_under_two_ranks_weak_line_carries_the_strong_point():
     """`--scaling weak`: every rank steps the configuration's 65 536 envs (`value` = all ranks' agent-steps over the slowest
-    rank's time), and the same run measures the configuration's batch split over the ranks as `strong`."""
-    out = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--scaling", "weak"])
+    rank's time), and with --full the same run measures the configuration's batch split over the ranks as `strong`."""
+    out = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--scaling", "weak",
+                     "--full"])
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout
@@ -100,9 +101,9 @@ def test_bench_under_two_ranks_weak_line_carries_the_strong_point():
 def test_bench_under_eight_ranks_prints_the_8_gpu_line():
     """`bench.py --gpus 8` as the driver launches it (one rank per GPU): the first real SCALE run must not fail on plumbing.
     The headline is the shape the north star's 1e8 agent-steps/s target is stated on: the 65 536 envs of C4 split over the
-    eight ranks (8192 each, the shape-specialised latency kernel); 65 536 envs on every rank ride along as `weak`."""
+    eight ranks (8192 each, the shape-specialised latency kernel); with --full, 65 536 envs on every rank ride along as `weak`."""
     _need_gpus(8)
-    out = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "5"], nproc=8, timeout=1500)
+    out = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "5", "--full"], nproc=8, timeout=1500)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout
@@ -124,7 +125,8 @@ def test_plain_bench_gpus_8_launches_itself():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("MGX_BENCH_ONE_GPU", "WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "5"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "5",
+                          "--full"],
                          capture_output=True, text=True, timeout=1500, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
