@@ -26,8 +26,8 @@ using namespace mgx;
 //   LockedHallway     the hallway holds up to max_hallway_keys keys and the A agents; a side room up to max_keys_per_room keys for
 //                     every time its colour comes up -- once with at most 6 rooms, ceil(rooms / 6) times beyond (the reference keys
 //                     its rooms by door colour, locked_hallway.py:168-190)
-//   Playground        unchanged (12 objects may draw one room, away from the agents' start; the reference itself gives up after
-//                     1000 tries there: roomgrid.py:255))
+//   Playground        a room holds the 12 objects and the A agents (all may draw one room; the reference itself gives up after 1000
+//                     tries: roomgrid.py:255); with fewer than 4 rooms, the start room also holds 12 objects away from the start)
 inline int check_layout_gen(const MgxSpec *spec, const MgxLayoutGen *gen) {
     const int W = spec->width, H = spec->height, rs = gen->room_size, A = spec->num_agents;
     const int room = (rs - 2) * (rs - 2);                       // free cells of one room
@@ -49,6 +49,10 @@ inline int check_layout_gen(const MgxSpec *spec, const MgxLayoutGen *gen) {
     }
     case MGX_GEN_PLAYGROUND:
         if (rs >= 4 && room < 12 + A + 1) return MGX_ERR_UNSUPPORTED;                  // all 12 objects may draw the same room
+        // ... and when that room is the agents' START room, the cells next to the start (5 of them) are closed to objects
+        // (reject_next_to): a room of size 6 then has 11 cells for 12 objects.  The reference raises there (place_in_room gives up
+        // after 1000 tries); place_io would never return.  Certain with one room, once in rooms^12 resets otherwise: refused below 4 rooms
+        if (rs >= 4 && room - 5 < 12 && ((W - 1) / (rs - 1)) * ((H - 1) / (rs - 1)) < 4) return MGX_ERR_UNSUPPORTED;
         break;
     default:
         break;

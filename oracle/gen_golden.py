@@ -21,6 +21,10 @@ Array conventions in the .npz files (reference layouts, narrowed to the smallest
     grid         (T,W,H,3), agents (T,A,9)  post-step state
     rng_final    (4,) u64
     spec_json    JSON: constructor-level parameters needed to rebuild the EnvSpec
+    resets_*.npz (record_resets: single resets from given generator states; product layout) hold other arrays:
+                 lay_before / npr_before / lay_after / npr_after u64[N,5], grid0 u8[N,H,W,3], agents0 u8[N,A,8], obs0, target,
+                 lay_halves / npr_halves, and the instrumentation tables calls / resamples / shuffles / key_draws / object_rooms
+                 (see record_resets' docstring)
     hook_order   (T,A) u8, only in the *_dictorder fixtures: the insertion order of the keys of the actions dict handed to
                  step() at step t (the RedBlueDoors / LockedHallway hooks iterate actions.items(), redbluedoors.py:176,
                  locked_hallway.py:210); every other fixture builds its dict in ascending agent order
@@ -325,6 +329,8 @@ def main():
     record_custom_steps(custom_envs.STEP_CASES_R6)
     record_edge()            # (behind everything older for the same reason)
     record_random_states()   # (constructs no registered env: every make_env() above keeps its construction seed)
+    record_resets()          # (likewise; both generators' states are set before every recorded reset)
+    record_reset_chains()
 
 
 def face(env, i, target_xy, carrying=None):
@@ -898,6 +904,426 @@ def record_random_states():
               f"truncated={int(rec['truncated'].sum()):4d} {os.path.getsize(path) / 1024:.1f} KiB")
     print(f"random-state corpus: {total / 1024:.1f} KiB")
     assert total <= 1 << 20, "the random-state corpus must stay within 1 MiB"
+
+
+# ---- the reset corpus (tests/golden/resets_*.npz): single resets of the REAL reference from given generator states ---------------
+#: (file tag, generator kind of the product, reference class name, constructor keywords, events)
+RESET_CONFIGS = [
+    ("empty_random_4_a3_full", "empty_random", "EmptyEnv", dict(size=4, agents=3, agent_view_size=3, agent_start_pos=None), 12),
+    ("empty_random_5_a8_full", "empty_random", "EmptyEnv", dict(size=5, agents=8, agent_view_size=3, agent_start_pos=None), 8),
+    ("empty_random_6_a3", "empty_random", "EmptyEnv", dict(size=6, agents=3, agent_view_size=5, agent_start_pos=None), 12),
+    ("empty_random_9_a4", "empty_random", "EmptyEnv", dict(size=9, agents=4, agent_start_pos=None), 12),
+    ("empty_random_16_a5", "empty_random", "EmptyEnv", dict(size=16, agents=5, agent_start_pos=None), 12),
+    ("empty_fixed_8_a2", "empty_fixed", "EmptyEnv", dict(size=8, agents=2), 4),
+    ("empty_fixed_5_a3", "empty_fixed", "EmptyEnv", dict(size=5, agents=3, agent_view_size=3, agent_start_pos=(2, 3), agent_start_dir=1), 4),
+    ("bup_rs4_a2_full", "blockedunlockpickup", "BlockedUnlockPickupEnv", dict(room_size=4, agents=2, agent_view_size=3), 12),
+    ("bup_rs5_a7_full", "blockedunlockpickup", "BlockedUnlockPickupEnv", dict(room_size=5, agents=7, agent_view_size=3), 8),
+    ("bup_rs5_a2", "blockedunlockpickup", "BlockedUnlockPickupEnv", dict(room_size=5, agents=2, agent_view_size=5), 12),
+    ("bup_rs6_a3", "blockedunlockpickup", "BlockedUnlockPickupEnv", dict(room_size=6, agents=3), 16),
+    ("bup_rs7_a2", "blockedunlockpickup", "BlockedUnlockPickupEnv", dict(room_size=7, agents=2), 12),
+    ("bup_rs8_a4", "blockedunlockpickup", "BlockedUnlockPickupEnv", dict(room_size=8, agents=4), 12),
+    ("bup_rs9_a2", "blockedunlockpickup", "BlockedUnlockPickupEnv", dict(room_size=9, agents=2), 12),
+    ("rbd_4_a4_full", "redbluedoors", "RedBlueDoorsEnv", dict(size=4, agents=4, agent_view_size=3), 12),
+    ("rbd_5_a2", "redbluedoors", "RedBlueDoorsEnv", dict(size=5, agents=2, agent_view_size=5), 12),
+    ("rbd_6_a3", "redbluedoors", "RedBlueDoorsEnv", dict(size=6, agents=3, agent_view_size=5), 12),
+    ("rbd_8_a3", "redbluedoors", "RedBlueDoorsEnv", dict(size=8, agents=3), 12),
+    ("rbd_12_a4", "redbluedoors", "RedBlueDoorsEnv", dict(size=12, agents=4), 12),
+    ("lh_2rooms_rs4_k11_a3_full", "lockedhallway", "LockedHallwayEnv",
+     dict(num_rooms=2, room_size=4, max_hallway_keys=1, max_keys_per_room=1, agents=3, agent_view_size=3), 12),
+    ("lh_2rooms_rs5_k33_a2", "lockedhallway", "LockedHallwayEnv",
+     dict(num_rooms=2, room_size=5, max_hallway_keys=3, max_keys_per_room=3, agents=2, agent_view_size=5), 12),
+    ("lh_4rooms_rs5_k12_a2", "lockedhallway", "LockedHallwayEnv",
+     dict(num_rooms=4, room_size=5, max_hallway_keys=1, max_keys_per_room=2, agents=2), 12),
+    ("lh_4rooms_rs4_k22_a2", "lockedhallway", "LockedHallwayEnv",
+     dict(num_rooms=4, room_size=4, max_hallway_keys=2, max_keys_per_room=2, agents=2, agent_view_size=5), 12),
+    ("lh_6rooms_rs5_k23_a3", "lockedhallway", "LockedHallwayEnv",
+     dict(num_rooms=6, room_size=5, max_hallway_keys=2, max_keys_per_room=3, agents=3), 12),
+    ("lh_8rooms_rs6_k23_a3", "lockedhallway", "LockedHallwayEnv",
+     dict(num_rooms=8, room_size=6, max_hallway_keys=2, max_keys_per_room=3, agents=3), 12),
+    ("lh_12rooms_rs4_k31_a2", "lockedhallway", "LockedHallwayEnv",
+     dict(num_rooms=12, room_size=4, max_hallway_keys=3, max_keys_per_room=1, agents=2, agent_view_size=5), 12),
+    ("lh_16rooms_rs7_k33_a4", "lockedhallway", "LockedHallwayEnv",
+     dict(num_rooms=16, room_size=7, max_hallway_keys=3, max_keys_per_room=3, agents=4), 8),
+    ("playground_1x1_rs7_a1", "playground", "PlaygroundEnv", dict(num_rows=1, num_cols=1, room_size=7, agents=1), 8),
+    ("playground_1x2_rs7_a2", "playground", "PlaygroundEnv", dict(num_rows=1, num_cols=2, room_size=7, agents=2), 12),
+    ("playground_2x3_rs6_a2", "playground", "PlaygroundEnv", dict(num_rows=2, num_cols=3, room_size=6, agents=2, agent_view_size=5), 12),
+    ("playground_3x3_rs7_a3", "playground", "PlaygroundEnv", dict(num_rows=3, num_cols=3, room_size=7, agents=3), 12),
+    ("playground_3x4_rs8_a1", "playground", "PlaygroundEnv", dict(num_rows=3, num_cols=4, room_size=8, agents=1), 8),
+    ("playground_4x4_rs6_a3", "playground", "PlaygroundEnv", dict(num_rows=4, num_cols=4, room_size=6, agents=3), 8),
+]
+#: the configurations whose pre-states are CONSTRUCTED so that a bounded draw re-samples (one per generator kind that draws)
+RESET_CONSTRUCTED = ["empty_random_6_a3", "bup_rs6_a3", "bup_rs7_a2", "rbd_6_a3", "lh_6rooms_rs5_k23_a3", "playground_2x3_rs6_a2"]
+_PCG_MULT = 0x2360ED051FC65DA44385DF649FCCF645
+_PCG_INV = pow(_PCG_MULT, -1, 1 << 128)
+_M128 = (1 << 128) - 1
+
+
+def _pcg_out(s):
+    hi, lo = s >> 64, s & M64
+    rot, x = hi >> 58, hi ^ lo
+    return ((x >> rot) | (x << ((64 - rot) & 63))) & M64
+
+
+def _gen_words5(gen):
+    st = gen.bit_generator.state
+    s, inc = int(st["state"]["state"]), int(st["state"]["inc"])
+    return np.array([s & M64, s >> 64, inc & M64, inc >> 64, (int(st["has_uint32"]) << 32) | int(st["uinteger"])], dtype=np.uint64)
+
+
+def _halves_between(before, after):
+    """32-bit draws made between two bit-generator states of one stream (position = 2 * words made - has_uint32)."""
+    s, inc, target = int(before["state"]["state"]), int(before["state"]["inc"]), int(after["state"]["state"])
+    words = 0
+    while s != target:
+        s = (s * _PCG_MULT + inc) & _M128
+        words += 1
+        assert words < 1 << 20
+    return 2 * words - int(after["has_uint32"]) + int(before["has_uint32"])
+
+
+def _half_stream(state, n):
+    """The next n 32-bit draws of a bit-generator state (numpy's next_uint32: the low half of a word, then its buffered high half)."""
+    s, inc = int(state["state"]["state"]), int(state["state"]["inc"])
+    out = [int(state["uinteger"])] if state["has_uint32"] else []
+    while len(out) < n:
+        s = (s * _PCG_MULT + inc) & _M128
+        w = _pcg_out(s)
+        out += [w & 0xFFFFFFFF, w >> 32]
+    return out[:n]
+
+
+def _lemire_rejects(half, span):
+    """Would Generator.integers over `span` values re-sample on this 32-bit draw?  (numpy's distributions.c, buffered_bounded_lemire_uint32)"""
+    return ((half * span) & 0xFFFFFFFF) < ((1 << 32) - span) % span
+
+
+def _constructed_state(base, k, high, salt):
+    """`base` (a bit-generator state dict) with its 128-bit state replaced so that word k from here (0 = the next one made) has a zero
+    low / high half: a next state with hi >> 58 == 0 (no rotation) and lo = hi ^ out, stepped back k + 1 times."""
+    inc = int(base["state"]["inc"])
+    r = np.random.default_rng([0x5E7, k, int(high), salt])
+    hi = int(r.integers(0, 1 << 58))
+    other = int(r.integers(1, 1 << 32))
+    out = other if high else other << 32
+    s = (hi << 64) | (hi ^ out)
+    for _ in range(k + 1):
+        s = ((s - inc) * _PCG_INV) & _M128
+    st = dict(base)
+    st["state"] = dict(state=s, inc=inc)
+    return st
+
+
+class _ResetProbe:
+    """Instrumentation from outside: wraps RandomMixin._rand_int / _rand_perm, MultiGridEnv.place_obj and RoomGrid.add_object of the
+    reference while a reset runs, and logs what the placement generator was asked for."""
+
+    def __init__(self):
+        from multigrid.base import MultiGridEnv
+        from multigrid.core.roomgrid import RoomGrid
+        from multigrid.utils.random import RandomMixin
+        self.targets = [(RandomMixin, "_rand_int"), (RandomMixin, "_rand_perm"), (MultiGridEnv, "place_obj"), (RoomGrid, "add_object")]
+        self.saved = [getattr(c, n) for c, n in self.targets]
+        self.clear()
+
+    def clear(self):
+        self.draws, self.calls, self.shuffles, self.rooms, self.in_call = [], [], [], [], None
+
+    def __enter__(self):
+        probe, (rand_int, rand_perm, place_obj, add_object) = self, self.saved
+
+        def _rand_int(env, low, high):
+            g = env._RandomMixin__np_random.bit_generator
+            before = g.state
+            v = rand_int(env, low, high)
+            span = int(high) - int(low)
+            n = _halves_between(before, g.state)
+            assert n == (span > 1) or (span > 1 and n > 1)
+            probe.draws.append(dict(lo=int(low), hi=int(high), value=int(v), halves=n, pending=int(before["has_uint32"]),
+                                    call=probe.in_call, before=before))
+            return v
+
+        def _rand_perm(env, iterable):
+            g = env._RandomMixin__np_random.bit_generator
+            before = g.state
+            out = rand_perm(env, iterable)
+            probe.shuffles.append(dict(n=len(out), halves=_halves_between(before, g.state), pending=int(before["has_uint32"])))
+            return out
+
+        def _place_obj(env, obj, top=None, size=None, reject_fn=None, max_tries=float("inf")):
+            assert probe.in_call is None
+            probe.in_call = len(probe.calls)
+            first = len(probe.draws)
+            before = env._RandomMixin__np_random.bit_generator.state
+            try:
+                return place_obj(env, obj, top, size, reject_fn, max_tries)
+            finally:
+                probe.calls.append(dict(first=first, ndraws=len(probe.draws) - first, before=before))
+                probe.in_call = None
+
+        def _add_object(env, col, row, kind=None, color=None):
+            probe.rooms.append(int(row) * env.num_cols + int(col))
+            return add_object(env, col, row, kind, color)
+
+        for (c, n), f in zip(self.targets, (_rand_int, _rand_perm, _place_obj, _add_object)):
+            setattr(c, n, f)
+        return self
+
+    def __exit__(self, *exc):
+        for (c, n), f in zip(self.targets, self.saved):
+            setattr(c, n, f)
+
+
+def _reset_event(env, probe, lay_state, npr_state, bup):
+    """One unseeded reset() of `env` from the two given bit-generator states -> (arrays, instrumentation rows)."""
+    lay, npr = env._RandomMixin__np_random, env.np_random
+    assert lay is not npr
+    lay.bit_generator.state, npr.bit_generator.state = lay_state, npr_state
+    A = env.num_agents
+    ev = dict(lay_before=_gen_words5(lay), npr_before=_gen_words5(npr))
+    probe.clear()
+    obs, _ = env.reset()
+    assert env._RandomMixin__np_random is lay and env.np_random is npr
+    ev.update(grid0=layouts_mod.grid_to_product(grid_with_contents(env)), agents0=layouts_mod.pack_agents(agents_with_contents(env)),
+              obs0=np.stack([obs[i]["image"] for i in range(A)]).astype(np.uint8), lay_after=_gen_words5(lay), npr_after=_gen_words5(npr),
+              lay_halves=_halves_between(lay_state, lay.bit_generator.state), npr_halves=_halves_between(npr_state, npr.bit_generator.state))
+    if bup:
+        ev["target"] = np.array([int(v) for v in np.asarray(env.obj)], dtype=np.uint8)
+    # call rows: [tries, x span, y span, real re-samples inside the call, a later try of the first fit's group of eight claims one]
+    calls, resamples = [], []
+    for ci, c in enumerate(probe.calls):
+        d = probe.draws[c["first"]:c["first"] + c["ndraws"]]
+        assert len(d) % 2 == 0 and len(d) >= 2
+        tries, xs, ys = len(d) // 2, d[0]["hi"] - d[0]["lo"], d[1]["hi"] - d[1]["lo"]
+        real = 0
+        for k, dr in enumerate(d):
+            if dr["halves"] > 1:
+                real += 1          # [generator, call, try, half of the rejected draw (1 = a pending high half), inside a call]
+                resamples.append([0, ci, k // 2, (dr["pending"] + 0) & 1, 1])
+        later = 0
+        if xs >= 2 and ys >= 2 and real == 0:
+            # what the lanes behind the fitting try of a group of eight would see: tries f + 1 .. 7 of that round, read as (x, y) draws
+            f = (tries - 1) % 8
+            hs = _half_stream(c["before"], 2 * (tries - 1 - f + 8))[2 * (tries - 1 - f):]
+            later = int(any(_lemire_rejects(hs[2 * j], xs) or _lemire_rejects(hs[2 * j + 1], ys) for j in range(f + 1, 8)))
+        calls.append([tries, xs, ys, real, later])
+    for dr in probe.draws:
+        if dr["call"] is None and dr["halves"] > 1:
+            resamples.append([0, -1, -1, dr["pending"] & 1, 0])
+    if bup and ev["npr_halves"] > 1:
+        resamples.append([1, -1, -1, int(npr_state["has_uint32"]) & 1, 0])
+    info = dict(calls=calls, resamples=resamples,
+                shuffles=[[s["n"], s["halves"] - (s["n"] - 1), s["pending"]] for s in probe.shuffles],
+                key_draws=[[dr["hi"] - 1, dr["value"]] for dr in probe.draws if dr["call"] is None and dr["lo"] == 1],
+                rooms=list(probe.rooms))
+    return ev, info
+
+
+def _reset_pre_states(tag, i):
+    """Event i's generator states: seeded PCG64 streams a few draws in; (i & 1, i & 2) = a pending 32-bit half on (placement, np_random)."""
+    out = []
+    for which in (0, 1):
+        g = np.random.Generator(np.random.PCG64([0x2E5E7, which, i] + [ord(c) for c in tag]))
+        g.random(i % 3)
+        if (i >> which) & 1:
+            g.integers(0, 5)
+            assert g.bit_generator.state["has_uint32"] == 1
+        out.append(g.bit_generator.state)
+    return out
+
+
+def _write_resets(fname, env, kind, kw, events, infos):
+    rec = {k: np.stack([e[k] for e in events]) for k in events[0] if k not in ("lay_halves", "npr_halves")}
+    for k in ("grid0", "agents0", "obs0"):
+        rec[k] = rec[k].astype(np.uint8)
+    rec["lay_halves"] = np.array([e["lay_halves"] for e in events], dtype=np.int32)
+    rec["npr_halves"] = np.array([e["npr_halves"] for e in events], dtype=np.int32)
+    for name, width in (("calls", 5), ("resamples", 5), ("shuffles", 3), ("key_draws", 2)):
+        rows = [[n] + list(r) for n, info in enumerate(infos) for r in info[name]]
+        rec[name] = np.asarray(rows, dtype=np.int32).reshape(-1, width + 1)
+    if kind == "playground":
+        rec["object_rooms"] = narrow(np.asarray([info["rooms"] for info in infos]))
+    gen = dict(kind=kind, room_size=int(kw.get("room_size", 0)), max_hallway_keys=int(kw.get("max_hallway_keys", 1)),
+               max_keys_per_room=int(kw.get("max_keys_per_room", 2)),
+               start=[int(v) for v in (*(kw.get("agent_start_pos", (1, 1)) or (1, 1)), kw.get("agent_start_dir", 0))])
+    env_kind = kind if kind in ("blockedunlockpickup", "redbluedoors", "lockedhallway") else "empty"
+    rec["spec_json"] = np.array(json.dumps(dict(spec_of_noreset(env, env_kind), gen=gen)))
+    path = os.path.join(OUT, fname + ".npz")
+    np.savez_compressed(path, **rec)
+    c = rec["calls"]
+    print(f"{fname:40s} events={len(events):3d} calls={len(c):4d} max tries={int(c[:, 1].max()) if len(c) else 0:3d} "
+          f"re-samples={len(rec['resamples']):2d} pending(lay,npr)={int((rec['lay_before'][:, 4] >> np.uint64(32)).sum())},"
+          f"{int((rec['npr_before'][:, 4] >> np.uint64(32)).sum())} {os.path.getsize(path) / 1024:.1f} KiB")
+    return os.path.getsize(path)
+
+
+def record_resets():
+    """The reset corpus: every file holds N independent unseeded reset() calls of ONE generator configuration of the real reference,
+    each from given states of its two generators (the placement generator `_RandomMixin__np_random` and `env.np_random`).  Arrays
+    (product layout; generator states as u64[5] = [state_lo, state_hi, inc_lo, inc_hi, has_uint32 << 32 | uinteger]):
+
+        lay_before, npr_before u64[N,5]      the two generators just before reset()
+        grid0 u8[N,H,W,3], agents0 u8[N,A,8], obs0 u8[N,A,v,v,3], target u8[N,3] (BlockedUnlockPickup: env.obj)
+        lay_after, npr_after u64[N,5]        the states the reset left
+        lay_halves, npr_halves i32[N]        32-bit draws each generator made
+        calls i32[M,6]       per place_obj call: [event, tries, x span, y span, re-samples inside the call, a LATER try of the fitting
+                             try's group of eight -- read as an (x, y) draw -- would claim a re-sample (what the group must ignore).
+                             This last column is COMPUTED by the recorder (_half_stream, _lemire_rejects: its own PCG64 and Lemire
+                             threshold over draws the reference never made), not observed; the re-samples the same model predicts
+                             inside a call are checked against the observed ones]
+        resamples i32[R,6]   per bounded draw that re-sampled: [event, generator (0 placement / 1 np_random), place_obj call (-1:
+                             outside), try, rejected draw was a pending high half, inside a place_obj call (= before its first fit)]
+        shuffles i32[S,4]    per Generator.shuffle (_rand_perm): [event, n, rejected masked draws, started on a pending half]
+        key_draws i32[K,3]   LockedHallway's key counts: [event, maximum, drawn]
+        object_rooms [N,12]  Playground: the room (row * cols + col) each of the 12 objects drew
+        spec_json            EnvSpec fields + "gen": the keywords of set_layout_generator
+
+    resets_con_*: the same configuration from CONSTRUCTED placement (and np_random) states whose word k has a zero low / high half,
+    so that a bounded draw over a span that is no power of two re-samples there; kept when the instrumentation shows an event of
+    a kind the file does not hold three of yet."""
+    global layouts_mod
+    sys.path.insert(0, REPO)
+    from multigrid_amd import layouts as layouts_mod
+    total = 0
+    with _ResetProbe() as probe:
+        for n, (tag, kind, cls_name, kw, N) in enumerate(RESET_CONFIGS):
+            cls = getattr(ref_envs, cls_name)
+            cls._default_seed = 0x5E7000 + n
+            env = cls(**kw)
+            env.reset(seed=n)
+            bup = kind == "blockedunlockpickup"
+            events, infos = [], []
+            for i in range(N):
+                ev, info = _reset_event(env, probe, *_reset_pre_states(tag, i), bup)
+                events.append(ev); infos.append(info)
+            total += _write_resets("resets_" + tag, env, kind, kw, events, infos)
+            if tag not in RESET_CONSTRUCTED:
+                continue
+            events, infos, have = [], [], {}
+            for k in range(41):
+                for high in (0, 1):
+                    for pend in (0, 1):
+                        lay_state, npr_state = _reset_pre_states(tag, 3 * pend)      # (event 3: a pending half on both generators)
+                        lay_state = _constructed_state(lay_state, k, high, n)
+                        if bup and k < 4:                                             # np_random's one draw: the door row
+                            npr_state = _constructed_state(npr_state, 0, high, n) if not pend else dict(npr_state, has_uint32=1, uinteger=0)
+                        ev, info = _reset_event(env, probe, lay_state, npr_state, bup)
+                        kinds = set()
+                        for r in info["resamples"]:
+                            kinds.add(("npr",) if r[0] == 1 else ("lay", r[3], r[4]))
+                        for c in info["calls"]:
+                            if c[4]:
+                                kinds.add(("later",))
+                            if c[3] and c[0] > 8:
+                                kinds.add(("second round",))
+                        new = [q for q in kinds if have.get(q, 0) < 3]
+                        if new:
+                            for q in kinds:
+                                have[q] = have.get(q, 0) + 1
+                            events.append(ev); infos.append(info)
+            total += _write_resets("resets_con_" + tag, env, kind, kw, events, infos)
+    print(f"reset corpus: {total / 1024:.1f} KiB")
+    assert total <= 800 << 10
+
+
+#: chained episodes: (file tag, generator kind, reference class, env id of the drop-in env, constructor keywords, steps)
+RESET_CHAINS = [
+    ("bup_rs6_a2", "blockedunlockpickup", "BlockedUnlockPickupEnv", "MultiGrid-BlockedUnlockPickup-v0", dict(room_size=6, agents=2, max_steps=7), 72),
+    ("bup_rs5_a3", "blockedunlockpickup", "BlockedUnlockPickupEnv", "MultiGrid-BlockedUnlockPickup-v0",
+     dict(room_size=5, agents=3, max_steps=5, agent_view_size=5), 60),
+    ("bup_rs8_a2", "blockedunlockpickup", "BlockedUnlockPickupEnv", "MultiGrid-BlockedUnlockPickup-v0", dict(room_size=8, agents=2, max_steps=9), 72),
+    ("empty_random_6_a3", "empty_random", "EmptyEnv", "MultiGrid-Empty-Random-6x6-v0",
+     dict(size=6, agents=3, max_steps=6, agent_view_size=5, agent_start_pos=None), 72),
+    ("empty_random_9_a2", "empty_random", "EmptyEnv", "MultiGrid-Empty-Random-6x6-v0",
+     dict(size=9, agents=2, max_steps=8, agent_start_pos=None), 72),
+]
+
+
+def record_reset_chains():
+    """Chained episodes (tests/golden/resets_chain_*.npz): ONE reference env object, small max_steps, scripted actions, an unseeded
+    reset() after every episode end -- what step(auto_reset=True) with device-side generation must reproduce step for step.  Some
+    episodes end EARLY: before a step, agent 0 is edited through its AgentState -- BlockedUnlockPickup: handed the target box (the
+    hook pays on the next step); Empty: put in front of the goal, facing it, and walked onto it.  The edit is an event of the
+    recording (`edit_step`, `edit_row`: agent 0's packed row after it) that a replay applies too.  The draw from env.np_random that
+    a reset makes comes after the ending step's action-order draw, at whatever step the episode ends.  Arrays (product layout):
+
+        lay0, npr0 u64[5]            the two generators before the FIRST unseeded reset (both on a pending 32-bit half)
+        actions i8[T,A], edit_step i32[K], edit_row u8[K,8]
+        obs u8[T,A,v,v,3], dir u8[T,A], reward f64[T,A], terminated u8[T,A], truncated u8[T]      every step's outputs
+        grid u8[T,H,W,3], agents u8[T,A,8], npr u64[T,5]     the state the step left (before the reset, where one follows)
+        done u8[T]                   an unseeded reset() follows step t;  reset_of i32[T]: its index r (-1: none)
+        grid0 u8[R,H,W,3], agents0 u8[R,A,8], obs0 u8[R,A,v,v,3], target u8[R,3], lay_after / npr_after u64[R,5]   reset r (0: the first)
+        spec_json                    EnvSpec fields, "gen" (set_layout_generator's keywords), "env_id" / "make" (the drop-in env)"""
+    sys.path.insert(0, REPO)
+    from multigrid_amd import layouts
+    FWD, DONE = 2, 6
+    for n, (tag, kind, cls_name, env_id, kw, T) in enumerate(RESET_CHAINS):
+        cls = getattr(ref_envs, cls_name)
+        cls._default_seed = 0xC4A10 + n
+        env = cls(**kw)
+        env.reset(seed=n)
+        bup = kind == "blockedunlockpickup"
+        A = env.num_agents
+        lay, npr = env._RandomMixin__np_random, env.np_random
+        lay.bit_generator.state, npr.bit_generator.state = _reset_pre_states("chain_" + tag, 3)
+        rec = dict(lay0=_gen_words5(lay), npr0=_gen_words5(npr))
+        resets = {k: [] for k in ("grid0", "agents0", "obs0", "target", "lay_after", "npr_after")}
+
+        def reset():
+            obs, _ = env.reset()
+            assert env._RandomMixin__np_random is lay and env.np_random is npr
+            resets["grid0"].append(layouts.grid_to_product(grid_with_contents(env)))
+            resets["agents0"].append(layouts.pack_agents(agents_with_contents(env)))
+            resets["obs0"].append(np.stack([obs[i]["image"] for i in range(A)]))
+            resets["target"].append([int(v) for v in np.asarray(env.obj)] if bup else [0, 0, 0])
+            resets["lay_after"].append(_gen_words5(lay)); resets["npr_after"].append(_gen_words5(npr))
+
+        reset()
+        r = np.random.default_rng(0xAC7 + n)
+        actions = r.choice(7, size=(T, A), p=[0.15, 0.15, 0.4, 0.08, 0.06, 0.08, 0.08]).astype(np.int8)
+        keys = ("obs", "dir", "reward", "terminated", "truncated", "grid", "agents", "npr", "done", "reset_of")
+        log = {k: [] for k in keys}
+        edit_step, edit_row = [], []
+        episode = 0
+        for t in range(T):
+            # every other episode ends early, at its 1st, 2nd, 3rd ... step in turn (never at the truncating one)
+            if episode % 2 == 1 and env.step_count == (episode // 2) % (env.max_steps - 1):
+                a0 = env.agents[0].state
+                if bup:
+                    a0.carrying = env.obj
+                    actions[t, 0] = DONE
+                else:
+                    a0.pos, a0.dir = (env.width - 3, env.height - 2), 0
+                    actions[t, 0] = FWD
+                edit_step.append(t); edit_row.append(layouts.pack_agents(agents_with_contents(env))[0])
+            obs, rew, term, trunc, _ = env.step({i: int(actions[t, i]) for i in range(A)})
+            log["obs"].append(np.stack([obs[i]["image"] for i in range(A)]))
+            log["dir"].append([int(obs[i]["direction"]) for i in range(A)])
+            log["reward"].append([float(rew[i]) for i in range(A)])
+            log["terminated"].append([bool(term[i]) for i in range(A)])
+            log["truncated"].append(bool(trunc[0]))
+            log["grid"].append(layouts.grid_to_product(grid_with_contents(env)))
+            log["agents"].append(layouts.pack_agents(agents_with_contents(env)))
+            log["npr"].append(_gen_words5(npr))
+            done = bool(env.is_done())
+            log["done"].append(done); log["reset_of"].append(len(resets["grid0"]) if done else -1)
+            if done:
+                reset()
+                episode += 1
+        rec["actions"] = actions
+        rec["edit_step"], rec["edit_row"] = np.asarray(edit_step, dtype=np.int32), np.asarray(edit_row, dtype=np.uint8).reshape(-1, 8)
+        for k in keys:
+            a = np.asarray(log[k])
+            rec[k] = a.astype(np.float64) if k == "reward" else a if k == "npr" else a.astype(np.int32) if k == "reset_of" else a.astype(np.uint8)
+        for k, v in resets.items():
+            rec[k] = np.asarray(v) if k.endswith("_after") else np.asarray(v).astype(np.uint8)
+        gen = dict(kind=kind, room_size=int(kw.get("room_size", 0)), max_hallway_keys=1, max_keys_per_room=2, start=[1, 1, 0])
+        mk = {k: (list(v) if isinstance(v, tuple) else v) for k, v in kw.items()}
+        rec["spec_json"] = np.array(json.dumps(dict(spec_of_noreset(env, kind if bup else "empty"), gen=gen, env_id=env_id, make=mk)))
+        path = os.path.join(OUT, "resets_chain_" + tag + ".npz")
+        np.savez_compressed(path, **rec)
+        early = int((rec["done"].astype(bool) & ~rec["truncated"].astype(bool)).sum())
+        print(f"{'resets_chain_' + tag:40s} T={T} resets={len(resets['grid0'])} early ends={early} truncations={int(rec['truncated'].sum())} "
+              f"{os.path.getsize(path) / 1024:.1f} KiB")
 
 
 def spec_of_noreset(env, kind):
