@@ -22,6 +22,8 @@
 //   P4   lane = cell: cells whose visibility bit is clear become UNSEEN (obs.py:95-100); packed cell -> (type, color, state),
 //        3 bytes each into the obs byte layout in LDS (the rotate/transpose)
 //   P5   ds_read_b128 -> buffer_store_dwordx4 of the (Gw,A,v,v,3) observation bytes
+// The one-step kernels with views of one lane pass on 16-bit tiles run P2 and P4 with one lane per view LINE instead (eight lanes
+// per slot, a lane holds the V cells of a view row; see-behind and visibility travel as one byte per line through LDS): gather_lines.
 //
 // Pure integer / byte work: no MFMA.  The roof is HBM bytes; what the kernel is actually bound by is the number of
 // VALU instructions per view, so the rules of the house are: every HBM byte touched once, 16-byte
@@ -758,6 +760,60 @@ __device__ __forceinline__ void gather_group_pk3(const KernelArgs &a, const int 
 #define MGX_GROUP 16
 #endif
 constexpr int kGroup = MGX_GROUP;      // slots gathered (P2) / written (P4) as one straight-line block
+
+// ---- P2 / P4 of the one-step kernels for views of one lane pass on 16-bit cells: one lane per view LINE (mgx_rules.h, "line map").
+// Pass p of the wavefront, lane l: view slot 8 p + (l >> 3), line j = l & 7 (the lanes with j >= V idle: 56 of 64 busy at 7x7, where
+// the cell map has 49).  Against one lane per cell this reads a view record once per 8 slots instead of once per slot, clamps the
+// forward distance once per line, and -- the larger part -- needs no transpose by v_writelane / v_readlane between the cell lanes
+// and the slot lanes of P3: a line's see-behind bits are one byte, stored at bytes[slot][j]; slot lane s reads its 8 bytes as
+// one 64-bit word (rows 8 bits apart: vis_mask_lines), writes the visibility word back in place, and P4's lanes read their byte.
+// `bytes`: u8[vpw][8], over the packed agent rows (LdsCarve::rows), which a one-step kernel has in registers from P1d on.
+__host__ __device__ __attribute__((always_inline)) constexpr bool view_line_lanes(int V, bool roll, bool one_hot, bool c8, int grp) {
+    return obs_dword_staging(V, roll) && V <= kLineLanes && !one_hot && !c8 && grp == kGroup && kGroup % kLineLanes == 0;
+}
+
+template <int V, int I>
+__device__ __forceinline__ void line_reads(const KernelArgs &a, const int wave, const int base, const int la_lo, const int la_hi,
+                                           const int stepL, uint32_t (&raw)[V]) {
+    if constexpr (I < V) {
+        const uint32_t addr = (uint32_t)line_cell_offset<I - V / 2>(base, la_lo, la_hi, stepL);
+        MGX_CHECK_LDS_ADDR(10, addr, 2);
+        raw[I] = gather_read<false>(addr);
+        line_reads<V, I + 1>(a, wave, base, la_lo, la_hi, stepL, raw);
+    }
+}
+
+// slots [S0, S0 + kGroup): whole groups, as gather_group (P1d pads a ragged last group's records with views of nothing)
+template <int V, int VPW, int S0>
+__device__ __forceinline__ void gather_lines(const KernelArgs &a, const int wave, const int lane, const int NVc, const ViewRec *rec,
+                                             uint8_t *bytes, uint32_t (&cellp)[VPW / kLineLanes][(V + 1) / 2]) {
+    if constexpr (S0 < VPW) {
+        if (S0 < NVc) {
+            constexpr int P0 = S0 / kLineLanes, PN = kGroup / kLineLanes;
+            const int j = lane & (kLineLanes - 1);
+            ViewRec r[PN];
+#pragma unroll
+            for (int q = 0; q < PN; ++q) {
+                MGX_CHECK_LDS_ADDR(11, (uint32_t)(uintptr_t)(lds_u32_ptr)(const void *)(rec + (P0 + q) * kLineLanes + (lane >> 3)), sizeof(ViewRec));
+                r[q] = rec[(P0 + q) * kLineLanes + (lane >> 3)];                    // (the 8 lanes of a slot read one address)
+            }
+            uint32_t raw[PN][V];
+#pragma unroll
+            for (int q = 0; q < PN; ++q)
+                line_reads<V, 0>(a, wave, line_base(r[q].origin, r[q].steps, r[q].lo, r[q].hi, V - 1 - j), clamp_hi16(r[q].lo),
+                                 clamp_hi16(r[q].hi), clamp_hi16(r[q].steps), raw[q]);
+#pragma unroll
+            for (int q = 0; q < PN; ++q) {
+#pragma unroll
+                for (int k = 0; k < (V + 1) / 2; ++k)
+                    cellp[P0 + q][k] = 2 * k + 1 < V ? (raw[q][2 * k] | (raw[q][2 * k + 1] << 16)) : raw[q][2 * k];
+                MGX_CHECK_LDS_ADDR(12, (uint32_t)(uintptr_t)(lds_u32_ptr)(const void *)(bytes + (P0 + q) * 64 + lane), 1);
+                bytes[(P0 + q) * 64 + lane] = (uint8_t)line_opaque_byte<V>(cellp[P0 + q]);     // == bytes[slot][j]
+            }
+        }
+        gather_lines<V, VPW, S0 + kGroup>(a, wave, lane, NVc, rec, bytes, cellp);
+    }
+}
 
 template <int V, int NW, int VPW, bool HALF, int G, bool C8 = false, int S0 = 0>
 __device__ __forceinline__ void gather_all(const KernelArgs &a, const int wave, int NVc, const ViewRec *rec,

@@ -43,6 +43,9 @@
     static_assert(NS <= 2, "slices: the (step, slice) sequence below is written for one or two");
     constexpr bool HALF = !DMA && (MODE == 1 || RSHAPE) && !C8;   // cell registers hold two slots' packed cells each (throughput step kernels)
     constexpr bool PK3 = kPack3<V>;              // 9x9 views: three views' 17-cell remainders share a lane pass (mgx_fused.h)
+    // LINES: P2 / P4 with one lane per view LINE instead of one per cell (mgx_fused.h gather_lines): the kernels of the dword staging
+    // on 16-bit tiles -- the same compile-time condition, no instantiation of its own
+    constexpr bool LINES = view_line_lanes(V, ROLL, OH, C8, GRP);
     // GRP: view slots gathered (P2) / written (P4) as one straight-line block and staged per P4/P5 round.  16 everywhere but in
     // the small-group latency instantiations (DMA, GRP 4 or 8), whose wavefronts own exactly ONE group: a wave of 4 views runs 4
     // slots of P2/P4/P5, not 16 -- on a lone wave's instruction chain that is the difference (fill_args picks them)
@@ -1150,6 +1153,14 @@
     uint32_t sbLo[NW], sbHi[NW];                 // lane s holds the see-behind ballot of slot s
 #pragma unroll
     for (int k = 0; k < NW; ++k) { sbLo[k] = 0; sbHi[k] = 0; }
+    // LINES: a lane's V cells of its line, two per register, for every pass of 8 slots; the lines' see-behind bytes [slot][line], then
+    // in place the visibility bytes, over the packed agent rows (dead: a one-step kernel has them in registers from P1d on)
+    [[maybe_unused]] uint32_t cellp[LINES ? VPW / kLineLanes : 1][(V + 1) / 2];
+    [[maybe_unused]] uint8_t *const line_bytes = L + cv.rows();
+    if constexpr (LINES) {
+        static_assert(!ROLL && !SLICED && NW == 1 && VPW % kGroup == 0, "line map: one-step kernels, views of one lane pass");
+        if (!MGX_DBG(4)) gather_lines<V, VPW, 0>(a, wave, lane, NVc, rec, line_bytes, cellp);
+    } else
     if (!MGX_DBG(4)) gather_all<V, NW, VPW, HALF, kG, C8>(a, wave, NVc, rec, lc, cell, sbLo, sbHi,
                                                           (uint32_t)(wave * wave_lds_ + cv.lut() + 512));
     if (ROLL) {                                                              // take the overlay off again: the tile persists
@@ -1163,6 +1174,24 @@
     uint32_t visLo[NW], visHi[NW];
 #pragma unroll
     for (int k = 0; k < NW; ++k) { visLo[k] = 0xffffffffu; visHi[k] = 0xffffffffu; }
+    if constexpr (LINES) {
+        // lane s: the 8 see-behind bytes of slot s as one word (rows 8 bits apart), flooded, written back as its visibility bytes
+        wave_sync();
+        if (lane < NVc) {
+            u32x2 *const w = reinterpret_cast<u32x2 *>(line_bytes) + lane;
+            MGX_CHECK_LDS_PTR(13, w, 8);
+            uint64_t vis = ~0ull;
+            if (masked && !MGX_DBG(8)) {
+                const u32x2 sbw = *w;
+                // (the bytes hold the cells' OPAQUE bits: see-behind is their complement)
+                const uint64_t sb = (~(((uint64_t)sbw.y << 32) | sbw.x) & ~(1ull << kLineOwnBit<V>))     // own cell: what it carries
+                                  | ((uint64_t)see_behind(my_carry) << kLineOwnBit<V>);
+                vis = vis_mask_lines<V>(sb);
+            }
+            *w = u32x2{(uint32_t)vis, (uint32_t)(vis >> 32)};
+        }
+        wave_sync();
+    } else
     if (masked && !MGX_DBG(8)) {
         uint64_t sb[NW], vis[NW];
 #pragma unroll
@@ -1351,10 +1380,45 @@
             }
         }
     };
+    // LINES: lane (slot, j)'s visibility byte of every pass, all read before the first round's staging stores
+    [[maybe_unused]] uint32_t line_vis[LINES ? VPW / kLineLanes : 1];
+    if constexpr (LINES) {
+#pragma unroll
+        for (int p = 0; p < VPW / kLineLanes; ++p) {
+            line_vis[p] = 0;
+            if (p * kLineLanes / kR * kR < NVc) {
+                MGX_CHECK_LDS_PTR(14, line_bytes + p * 64 + lane, 1);
+                line_vis[p] = line_bytes[p * 64 + lane];
+            }
+        }
+    }
 #pragma unroll
     for (int r0 = 0; r0 < VPW; r0 += kR) {
         if (r0 < NVc) {
             if (!MGX_DBG(16)) {
+                if constexpr (LINES) {
+                    // lane (slot, j) masks and unpacks the V cells of its line and stores them at image[i][j] = cell i*V + j of its
+                    // slot: the round's two passes of 8 slots, straight-line (whole groups; padding slots write junk that P5 never copies)
+                    constexpr int PR = kR / kLineLanes;
+                    const int lj = lane & (kLineLanes - 1);
+                    if (lj < V) {
+                        uint32_t *const dl = stg + (lane >> 3) * V2 + lj;
+#pragma unroll
+                        for (int q = 0; q < PR; ++q) {
+                            const uint32_t vb = line_vis[r0 / kLineLanes + q];
+#pragma unroll
+                            for (int k = 0; k < (V + 1) / 2; ++k) {
+                                const uint32_t x = cellp[r0 / kLineLanes + q][k];
+                                const uint32_t tc = x & 0x070f070fu, st = (x >> 12) & 0x00030003u;
+#pragma unroll
+                                for (int i = 2 * k; i < 2 * k + 2 && i < V; ++i) {
+                                    MGX_CHECK_LDS_PTR(5, dl + q * kLineLanes * V2 + i * V, 4);
+                                    dl[q * kLineLanes * V2 + i * V] = line_stage_cell(tc, st, i, vb);
+                                }
+                            }
+                        }
+                    }
+                } else
                 if (lc.act[0]) {
                     // whole groups of kG slots, like P2 (padding slots write junk into staging space that P5 never copies):
                     // straight-line code whose readlane -> select -> write chains overlap

@@ -791,6 +791,90 @@ MGX_HD int clamped_offset(int origin, const ViewClamp &c, int fw, int la) {
     return origin + f * lo16(c.steps) + l * hi16(c.steps);
 }
 
+// ---------------------------------------------------------------------------------------------------
+// The LINE map of the one-step kernels' P2 / P4 for views of one lane pass (mgx_fused.h gather_lines): eight lanes per view slot,
+// lane (slot, j) owns view row j -- the V cells image[0..V-1][j] at ONE forward distance fw = V-1-j -- two cells per register
+// (cell i in half i & 1 of pair i >> 1).  The see-behind and visibility words of a view then hold row j in bits [8j, 8j + V):
+// one byte per line, which is what a line's lane writes (P2) and reads back (P4) through LDS.
+// ---------------------------------------------------------------------------------------------------
+constexpr int kLineLanes = 8;            // lanes per view slot == bit stride of a view row in the line map's 64-bit words
+
+MGX_HD int clamp_hi16(uint32_t v) { return (int32_t)v >> 16; }     // the lateral (high) half of a ViewClamp word
+
+// tile offset of line fw at lateral offset 0: origin + fw' * stepF, fw' = fw clamped as clamped_offset clamps it.  The forward
+// clamp and the multiply happen once per line instead of once per cell (v_pk_max_i16, v_pk_min_i16, v_and, v_dot2_i32_i16).
+MGX_HD int line_base(int origin, uint32_t steps, uint32_t lo, uint32_t hi, int fw) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint32_t t;
+    int r;
+    asm("v_pk_max_i16 %0, %1, %2" : "=v"(t) : "v"((uint32_t)fw & 0xffffu), "v"(lo));
+    asm("v_pk_min_i16 %0, %1, %2" : "=v"(t) : "v"(t), "v"(hi));
+    asm("v_dot2_i32_i16 %0, %1, %2, %3" : "=v"(r) : "v"(t & 0xffffu), "v"(steps), "v"(origin));
+    return r;
+#else
+    const int l = (int)(int16_t)(lo & 0xffffu), h = (int)(int16_t)(hi & 0xffffu);
+    int f = fw > l ? fw : l;
+    f = f < h ? f : h;
+    return origin + f * (int)(int16_t)(steps & 0xffffu);
+#endif
+}
+
+// ... of the line's cell at lateral offset LA (a constant of the unrolled cell loop): base + med3(LA, la_lo, la_hi) * stepL.
+// The median IS the clamp min(max(LA, la_lo), la_hi) whenever la_lo <= la_hi, which every record has (a valid view's imin <= imax;
+// the record of an invalid or a padding view is all zeros).  One v_med3_i32 with LA inline + one v_mad_i32_i24 per cell.
+template <int LA>
+MGX_HD int line_cell_offset(int base, int la_lo, int la_hi, int stepL) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    int l, r;
+    asm("v_med3_i32 %0, %1, %2, %3" : "=v"(l) : "n"(LA), "v"(la_lo), "v"(la_hi));
+    asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(r) : "v"(l), "v"(stepL), "v"(base));
+    return r;
+#else
+    const int mn = la_lo < la_hi ? la_lo : la_hi, mx = la_lo < la_hi ? la_hi : la_lo;
+    const int l = LA < mn ? mn : (LA > mx ? mx : LA);                           // median of three
+    return base + l * stepL;
+#endif
+}
+
+// the line's see-behind byte: bit i = the opaque bit (bit 15) of the packed 16-bit cell i
+template <int V>
+MGX_HD uint32_t line_opaque_byte(const uint32_t (&pr)[(V + 1) / 2]) {
+    uint32_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < (V + 1) / 2; ++k) acc |= ((pr[k] & 0x80008000u) >> 15) << (2 * k);   // even cells: bit 2k, odd: bit 16 + 2k
+    return (acc | (acc >> 15)) & 0xffu;
+}
+
+// vis_mask on the line map's words: rows kLineLanes bits apart, bits [V, 8) of every row ignored on the way in and zero on the way out
+template <int V>
+MGX_HD uint64_t vis_mask_lines(uint64_t sb) {
+    static_assert(V <= kLineLanes && V * kLineLanes <= 64, "line map: views of up to 8 rows of up to 8 cells");
+    constexpr uint32_t F = (1u << V) - 1u;
+    uint64_t vis = 0;
+    uint32_t init = 1u << (V / 2);
+    init |= brev32(init);
+#pragma unroll
+    for (int j = V - 1; j >= 0; --j) {                                // (the flood itself: vis_mask above, row for row)
+        const uint32_t s0 = (uint32_t)(sb >> (kLineLanes * j)) & F;
+        const uint32_t s = s0 | brev32(s0);
+        uint32_t u = ((s + (init & s)) ^ s) | init;
+        u |= brev32(u);
+        vis |= (uint64_t)(u & F) << (kLineLanes * j);
+        const uint32_t p = u & s;
+        init = p | (p << 1) | (p >> 1);
+    }
+    return vis;
+}
+// bit of the agent's own cell image[V/2][V-1] in such a word
+template <int V> constexpr int kLineOwnBit = (V - 1) * kLineLanes + V / 2;
+
+// P4 of a line: cell i (half i & 1 of its pair register x; tc = x & 0x070f070f, st = (x >> 12) & 0x00030003, as obs_stage_sel wants
+// them) as the staged dword (type, color, state, 0), or UNSEEN = (0, 0, 0) when bit i of the line's visibility byte is clear
+MGX_HD uint32_t line_stage_cell(uint32_t tc, uint32_t st, int i, uint32_t vis_byte) {
+    const uint32_t c = perm_b32(st, tc, obs_stage_sel((i & 1) != 0));
+    return c & (uint32_t)((int32_t)(vis_byte << (31 - i)) >> 31);               // (v_bfe_i32 + v_and)
+}
+
 // in-bounds bit mask in lane order k = j*V + i
 template <int V, int NW>
 MGX_HD void inbounds_mask(const ViewGeom &g, uint64_t (&m)[NW]) {
