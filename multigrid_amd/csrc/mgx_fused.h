@@ -89,7 +89,7 @@ struct KernelArgs {
     int32_t inv_A;      // ceil(2^16 / A): (lane * inv_A) >> 16 == lane / A for lane < 64
     int32_t ns;         // rollout / persistent launches: slices of Gw envs per wavefront (LdsCarve); 0 = the ordinary kernels, 1 / 2 = a
                         // resident shape (kShapes[].ns): host-side geometry, the kernels have it as a constant
-    int32_t rshape;     // ... which one (kShapes index; fill_args chose it)
+    int32_t rshape;     // ... which one (kShapes index; plan_launch chose it)
     // fused auto-reset (mgx_step_autoreset / mgx_rollout_autoreset; include/mgx.h: MgxAutoReset)
     int32_t pool_size;
     int64_t first_env;
@@ -342,19 +342,41 @@ __host__ __device__ __attribute__((always_inline)) inline LdsCarve make_carve(in
 inline int cell_bytes_of(const MgxSpec &sp) { return sp.cell_bytes == 1 ? 1 : kCellBytes; }        // the LDS tile's cells
 inline int grid_cell_bytes_of(const MgxSpec &sp) { return sp.cell_bytes == 3 ? 3 : cell_bytes_of(sp); }   // the HBM tensors' cells
 
-// `grp`: the group size the launch's instantiation is compiled for (16, or 4 / 8: KernelArgs::grp)
-inline int slots_in_use(const MgxSpec &sp, int Gw, bool narrow = false, int grp = 16) {
-    int vpw = (Gw * sp.num_agents + grp - 1) / grp * grp;     // (the kernel is compiled for slots_per_wave(V) slots)
-    const int cap = slots_per_wave(sp.view_size, narrow || sp.cell_bytes == 1);   // (compact cells: one decoded cell per register)
-    return vpw > cap ? cap : vpw;
-}
-
-inline int wave_lds_bytes(const MgxSpec &sp, int Gw, bool roll = false, bool one_hot = false, bool obs_only = false, int grp = 16) {
-    return make_carve(sp.width, sp.height, sp.num_agents, sp.view_size, Gw, slots_in_use(sp, Gw, roll || obs_only, grp), roll,
-                      sp.env_kind != MGX_KIND_EMPTY, one_hot, grp, cell_bytes_of(sp)).total();
-}
+// WHAT is launched, as a value: the kernel family (the MODE template parameter of mgx_fused_kernel) and the two options that select
+// an instantiation.  Every launch decision of the host is a function of (spec, batch, form): the specs a form serves and its geometry
+// (mgx_kernels.hip: check_spec, plan_launch), a wavefront's view slots and LDS carve (below), the instantiation (launch_view).
+struct LaunchForm {
+    enum Family : int { kGenObs = 0, kStep = 1, kRollout = 2, kPersistent = 3 };
+    enum : int { kOneHot = 4, kGenerate = 8 };             // (bits of mode())
+    Family family;
+    bool one_hot = false;     // observations written one-hot encoded
+    bool generate = false;    // finished envs are regenerated in the tail of the launch (one step only)
+    static constexpr LaunchForm gen_obs() { return {kGenObs}; }       static constexpr LaunchForm step() { return {kStep}; }
+    static constexpr LaunchForm rollout() { return {kRollout}; }      static constexpr LaunchForm persistent() { return {kPersistent}; }
+    constexpr LaunchForm with_one_hot(bool on = true) const { return {family, on, generate}; }
+    constexpr LaunchForm with_generate(bool on = true) const { return {family, one_hot, on}; }
+    constexpr bool roll() const { return family == kRollout || family == kPersistent; }   // the state lives in LDS across steps
+    constexpr bool persist() const { return family == kPersistent; }
+    constexpr bool obs_only() const { return family == kGenObs; }
+    constexpr bool narrow() const { return roll() || obs_only(); }                         // (slots_per_wave: `narrow`)
+    // the plain step: the only form with shape-specialised, runtime-compiled and small-group instantiations (kShapes, has_small_groups)
+    constexpr bool plain_step() const { return family == kStep && !one_hot && !generate; }
+    constexpr int mode() const { return family | (one_hot ? kOneHot : 0) | (generate ? kGenerate : 0); }   // what launch_view switches on
+};
 
 constexpr int kGroupSlots = 16;           // (== kGroup, defined with the gather below)
+// view slots the instantiations of `form` are compiled for (compact cells: one decoded cell per register)
+inline int form_slots(const MgxSpec &sp, LaunchForm form) { return slots_per_wave(sp.view_size, form.narrow() || sp.cell_bytes == 1); }
+// `grp`: the group size the launch's instantiation is compiled for (16, or 4 / 8: KernelArgs::grp)
+inline int slots_in_use(const MgxSpec &sp, int Gw, LaunchForm form, int grp) {
+    const int vpw = (Gw * sp.num_agents + grp - 1) / grp * grp, cap = form_slots(sp, form);
+    return vpw > cap ? cap : vpw;
+}
+inline int wave_lds_bytes(const MgxSpec &sp, int Gw, LaunchForm form, int grp) {
+    return make_carve(sp.width, sp.height, sp.num_agents, sp.view_size, Gw, slots_in_use(sp, Gw, form, grp), form.roll(),
+                      sp.env_kind != MGX_KIND_EMPTY, form.one_hot, grp, cell_bytes_of(sp)).total();
+}
+
 constexpr int kLdsPerCU = 160 * 1024;
 #ifndef MGX_LDS_WAVE_BUDGET
 #define MGX_LDS_WAVE_BUDGET (12 * 1024)
@@ -363,10 +385,10 @@ constexpr int kLdsWaveBudget = MGX_LDS_WAVE_BUDGET;     // keeps >= 12 wavefront
 
 // Envs per wavefront: as many as fit the wave's view slots and its LDS budget; fewer when the batch is too small
 // to give every SIMD of the chip a few wavefronts (then latency, not throughput, is what matters).
-inline int choose_Gw(const MgxSpec &sp, int64_t batch, bool roll = false, bool one_hot = false, bool obs_only = false) {
-    int Gw = slots_per_wave(sp.view_size, roll || obs_only || sp.cell_bytes == 1) / sp.num_agents;
+inline int choose_Gw(const MgxSpec &sp, int64_t batch, LaunchForm form) {
+    int Gw = form_slots(sp, form) / sp.num_agents;
     if (Gw < 1) Gw = 1;
-    while (Gw > 1 && wave_lds_bytes(sp, Gw, roll, one_hot, obs_only) > kLdsWaveBudget) --Gw;
+    while (Gw > 1 && wave_lds_bytes(sp, Gw, form, kGroupSlots) > kLdsWaveBudget) --Gw;
     // a power of two: otherwise the tile's 16-byte vectors and the output rows stop lining up with the wave's lanes (round 2:
     // C4 at 14 envs per wave 30.4 us, 12: 22.1, 16: 20.8)
     while (Gw > 2 && (Gw & (Gw - 1)) != 0) Gw &= Gw - 1;
@@ -907,7 +929,7 @@ inline int match_fixed_shape(const KernelArgs &ka, bool hooks, bool persist = fa
     return 0;
 }
 
-// ... and which RESIDENT shape (kShapes[].ns > 0) the geometry of a rollout / persistent launch is: fill_args chose it (ka.ns), this
+// ... and which RESIDENT shape (kShapes[].ns > 0) the geometry of a rollout / persistent launch is: plan_launch chose it (ka.ns), this
 // re-checks every number the instantiation was compiled for.
 inline int match_resident_shape(const KernelArgs &ka, bool hooks) {
     if (MGX_NO_FIXED_SHAPES || ka.grp != kGroup || ka.ns < 1 || ka.rshape < 1 || ka.rshape >= kNumShapes) return 0;
@@ -923,8 +945,24 @@ inline int match_resident_shape(const KernelArgs &ka, bool hooks) {
 // the host derived, exactly like the built-in kShapes entries.  fn[ar]: the plain step without / with the fused auto-reset.
 struct JitShape { FixedShape f; int vpw, wave_lds; hipFunction_t fn[2]; };
 const JitShape *jit_shape_lookup(const KernelArgs &ka, bool hooks);
+// The tail of every launcher below: `kern` with the plan's geometry -- or, `occupancy`: query only (mgx_sub_shards, the persistent
+// launch's residency check), the workgroups of this instantiation that one CU holds at a time.
+inline int launch_kernel(void (*kern)(const KernelArgs), const KernelArgs &ka, int threads, int lds_bytes, int64_t nwg, hipStream_t stream,
+                         int *hip_err, int *occupancy) {
+    hipError_t e = hipSuccess;
+    if (lds_bytes > 64 * 1024) e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+    if (e == hipSuccess && occupancy)
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(occupancy, reinterpret_cast<const void *>(kern), threads, (size_t)lds_bytes);
+    if (e != hipSuccess) { *hip_err = (int)e; (void)hipGetLastError(); return MGX_ERR_LAUNCH; }   // (off HIP's sticky state too)
+    if (occupancy) return MGX_OK;
+    hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(threads), (size_t)lds_bytes, stream, ka);
+    e = hipGetLastError();
+    if (e != hipSuccess) { *hip_err = (int)e; return MGX_ERR_LAUNCH; }
+    return MGX_OK;
+}
+
 // Compact cells (C8): the plain step / gen_obs of the throughput and streamed families -- hooks and auto-reset included, no one-hot,
-// generation, rollout or latency (LDS-DMA) instantiation: fill_args never asks for one on such a spec.
+// generation, rollout or latency (LDS-DMA) instantiation: plan_launch never asks for one on such a spec.
 // (... and, with C8 = false / B3 = true, the byte-grid family: the same set of kernels for MgxSpec.cell_bytes = 3)
 template <int V, int MODE, bool STREAM, bool C8 = true, bool OH = false>
 inline int launch_compact(const KernelArgs &ka, int threads, int lds_bytes, int64_t nwg, hipStream_t stream, int *hip_err, int *occupancy) {
@@ -936,19 +974,7 @@ inline int launch_compact(const KernelArgs &ka, int threads, int lds_bytes, int6
         const bool ar = ka.pool_grid != nullptr;
         void (*kern)(const KernelArgs) = ar ? mgx_fused_kernel<V, MODE, false, true, false, false, false, false, kGroup, 0, true, false>
                                             : mgx_fused_kernel<V, MODE, false, false, false, false, false, false, kGroup, 0, true, false>;
-        if (lds_bytes > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-            if (e != hipSuccess) { *hip_err = (int)e; (void)hipGetLastError(); return MGX_ERR_LAUNCH; }
-        }
-        if (occupancy) {
-            hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(occupancy, reinterpret_cast<const void *>(kern), threads, (size_t)lds_bytes);
-            if (e != hipSuccess) { *hip_err = (int)e; (void)hipGetLastError(); return MGX_ERR_LAUNCH; }
-            return MGX_OK;
-        }
-        hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(threads), (size_t)lds_bytes, stream, ka);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { *hip_err = (int)e; return MGX_ERR_LAUNCH; }
-        return MGX_OK;
+        return launch_kernel(kern, ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
     } else if constexpr (MODE > 1 || (OH && (MODE != 1 || !C8))) {
         return MGX_ERR_UNSUPPORTED;
     } else {
@@ -989,20 +1015,7 @@ inline int launch_compact(const KernelArgs &ka, int threads, int lds_bytes, int6
                              : (ar ? mgx_fused_kernel<V, MODE, false, S, false, false, STREAM, false, kGroup, 0, C8, B3>
                                    : mgx_fused_kernel<V, MODE, false, false, false, false, STREAM, false, kGroup, 0, C8, B3>);
         }
-        if (lds_bytes > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-            if (e != hipSuccess) { *hip_err = (int)e; (void)hipGetLastError(); return MGX_ERR_LAUNCH; }
-        }
-        if (occupancy) {
-            hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(occupancy, reinterpret_cast<const void *>(kern), threads,
-                                                                        (size_t)lds_bytes);
-            if (e != hipSuccess) { *hip_err = (int)e; (void)hipGetLastError(); return MGX_ERR_LAUNCH; }
-            return MGX_OK;
-        }
-        hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(threads), (size_t)lds_bytes, stream, ka);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { *hip_err = (int)e; return MGX_ERR_LAUNCH; }
-        return MGX_OK;
+        return launch_kernel(kern, ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
     }
 }
 
@@ -1041,7 +1054,7 @@ inline int launch_mode(const KernelArgs &ka, int threads, int lds_bytes, int64_t
     // the shape-specialised instantiations (kShapes): the plain step of the latency family at 7x7 views, picked only when the
     // launch geometry the host derived is exactly the one the instantiation was compiled for
     if constexpr (MODE == 1 && !OH && !GEN && GRP == kGroup && !MGX_NO_FIXED_SHAPES) {
-        const int shape = match_fixed_shape(ka, hooks);          // (its V / dma / stream are this instantiation's: fill_args set the flags)
+        const int shape = match_fixed_shape(ka, hooks);          // (its V / dma / stream are this instantiation's: plan_launch set the flags)
         if constexpr (V == 7 && DMA && !STREAM) {
             switch (shape) {
             case 1: kern = ar ? mgx_fused_kernel<V, 1, false, true, false, false, false, true, kGroup, 1> : mgx_fused_kernel<V, 1, false, false, false, false, false, true, kGroup, 1>; break;
@@ -1076,7 +1089,7 @@ inline int launch_mode(const KernelArgs &ka, int threads, int lds_bytes, int64_t
             if constexpr (MODE == 2) kern = ar ? mgx_resident_kernel<2, true> : mgx_resident_kernel<2, false>;
             else return MGX_ERR_INVALID_ARGUMENT;
             break;
-        default: if (ka.ns > 0) return MGX_ERR_INVALID_ARGUMENT;               // (fill_args chose a geometry no instantiation has)
+        default: if (ka.ns > 0) return MGX_ERR_INVALID_ARGUMENT;               // (plan_launch chose a geometry no instantiation has)
         }
     } else if (ka.ns > 0) return MGX_ERR_INVALID_ARGUMENT;
     if constexpr (MODE == 1 && !OH && !GEN && GRP == kGroup && !MGX_NO_FIXED_SHAPES) {
@@ -1107,49 +1120,37 @@ inline int launch_mode(const KernelArgs &ka, int threads, int lds_bytes, int64_t
                          : (ar ? mgx_fused_kernel<V, MODE, false, S, OH, false, STREAM, DMA, GRP> : mgx_fused_kernel<V, MODE, false, false, OH, false, STREAM, DMA, GRP>);
         }
     }
-    if (lds_bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-        if (e != hipSuccess) { *hip_err = (int)e; (void)hipGetLastError(); return MGX_ERR_LAUNCH; }   // (off HIP's sticky state too)
-    }
-    if (occupancy) {        // query only (mgx_sub_shards): workgroups of this instantiation that one CU holds at a time
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(occupancy, reinterpret_cast<const void *>(kern), threads,
-                                                                    (size_t)lds_bytes);
-        if (e != hipSuccess) { *hip_err = (int)e; (void)hipGetLastError(); return MGX_ERR_LAUNCH; }
-        return MGX_OK;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(threads), (size_t)lds_bytes, stream, ka);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { *hip_err = (int)e; return MGX_ERR_LAUNCH; }
-    return MGX_OK;
+    return launch_kernel(kern, ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
 }
 
 template <int V>
-inline int launch_view(int mode, const KernelArgs &ka, int threads, int lds_bytes, int64_t nwg, hipStream_t stream,
+inline int launch_view(LaunchForm form, const KernelArgs &ka, int threads, int lds_bytes, int64_t nwg, hipStream_t stream,
                        int *hip_err, int *occupancy) {
-    switch (mode) {                     // mode | 4: one-hot observations; | 8: tail generation (one step only)
-    case 0: return launch_mode<V, 0, false>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
-    case 1: return launch_mode<V, 1, false>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
-    case 2: return launch_mode<V, 2, false>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
-    case 3:                                                                                                // persistent stepping
+    using F = LaunchForm;
+    switch (form.mode()) {
+    case F::gen_obs().mode(): return launch_mode<V, F::kGenObs, false>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
+    case F::step().mode(): return launch_mode<V, F::kStep, false>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
+    case F::rollout().mode(): return launch_mode<V, F::kRollout, false>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
+    case F::persistent().mode():
         // (hipcc 7.2 crashes at -O3 on the persistent kernels of the three largest views with the bounds checks / the debug knobs
         // compiled in.  The checked and the tools' builds compile those units at -O2 (multigrid_amd/build.py: flags) and carry
         // them; only the single-translation-unit timestamps build, which wants -O3 code for its stamps, leaves them out.)
         if constexpr (MGX_NO_BIG_PERSIST != 0 && V >= 11) return MGX_ERR_UNSUPPORTED;
-        else return launch_mode<V, 3, false>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
-    case 4: return launch_mode<V, 0, true>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
-    case 5: return launch_mode<V, 1, true>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
-    case 6: return launch_mode<V, 2, true>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
-    case 9: return launch_mode<V, 1, false, true>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);   // | 8: generate
-    case 13: return launch_mode<V, 1, true, true>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
-    default: return MGX_ERR_INVALID_ARGUMENT;
+        else return launch_mode<V, F::kPersistent, false>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
+    case F::gen_obs().with_one_hot().mode(): return launch_mode<V, F::kGenObs, true>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
+    case F::step().with_one_hot().mode(): return launch_mode<V, F::kStep, true>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
+    case F::rollout().with_one_hot().mode(): return launch_mode<V, F::kRollout, true>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
+    case F::step().with_generate().mode(): return launch_mode<V, F::kStep, false, true>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
+    case F::step().with_one_hot().with_generate().mode():
+        return launch_mode<V, F::kStep, true, true>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
+    default: return MGX_ERR_INVALID_ARGUMENT;      // (no such instantiation: generation is the one-step kernels' tail)
     }
 }
 
 // One translation unit per view size (mgx_fused_inst.hip, -DMGX_INST_V=<V>) defines its launcher:
 #define MGX_FOR_EACH_VIEW(X) X(3) X(5) X(7) X(9) X(11) X(13) X(15)
 #define MGX_DECLARE_LAUNCHER(V) \
-    int launch_v##V(int mode, const KernelArgs &ka, int threads, int lds_bytes, int64_t nwg, hipStream_t stream, int *hip_err, \
+    int launch_v##V(LaunchForm form, const KernelArgs &ka, int threads, int lds_bytes, int64_t nwg, hipStream_t stream, int *hip_err, \
                     int *occupancy);
 MGX_FOR_EACH_VIEW(MGX_DECLARE_LAUNCHER)
 #undef MGX_DECLARE_LAUNCHER

@@ -48,7 +48,7 @@
     constexpr bool LINES = view_line_lanes(V, ROLL, OH, C8, GRP);
     // GRP: view slots gathered (P2) / written (P4) as one straight-line block and staged per P4/P5 round.  16 everywhere but in
     // the small-group latency instantiations (DMA, GRP 4 or 8), whose wavefronts own exactly ONE group: a wave of 4 views runs 4
-    // slots of P2/P4/P5, not 16 -- on a lone wave's instruction chain that is the difference (fill_args picks them)
+    // slots of P2/P4/P5, not 16 -- on a lone wave's instruction chain that is the difference (plan_launch picks them)
     constexpr int kG = GRP, kR = SLICED ? kRoundResident : GRP;   // (sliced kernels: the staging of a round lies over the view records: 8 slots)
     constexpr int kG4 = kR < kG ? kR : kG;                          // P4's straight-line blocks: within one round
     constexpr int VPW = (DMA && GRP < kGroup) ? GRP : ((V <= 7 && HALF) ? kSlotsSmallView : 32);   // view slots per wavefront

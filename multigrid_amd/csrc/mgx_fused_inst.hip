@@ -8,11 +8,14 @@
 #define MGX_CAT2(a, b) a##b
 #define MGX_CAT(a, b) MGX_CAT2(a, b)
 
+#if !defined(MGX_ONLY_V) || MGX_ONLY_V == MGX_INST_V        // (-DMGX_ONLY_V=<v>: a single-translation-unit build of that view size alone)
 namespace mgx_fused {
-int MGX_CAT(launch_v, MGX_INST_V)(int mode, const KernelArgs &ka, int threads, int lds_bytes, int64_t nwg, hipStream_t stream,
+int MGX_CAT(launch_v, MGX_INST_V)(LaunchForm form, const KernelArgs &ka, int threads, int lds_bytes, int64_t nwg, hipStream_t stream,
                                   int *hip_err, int *occupancy) {
-    return launch_view<MGX_INST_V>(mode, ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
+    return launch_view<MGX_INST_V>(form, ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
 }
 }  // namespace mgx_fused
+#endif
 #undef MGX_CAT
 #undef MGX_CAT2
+#undef MGX_INST_V

@@ -9,51 +9,26 @@
 
 #if MGX_SINGLE_TU      // (tools' builds that need the kernels and the host code in one module, e.g. -DMGX_SPANS=1: kernel-side
                        // globals); -DMGX_ONLY_V=<v> keeps just that view size (a third of the build time)
-#define MGX_TU_HAS(v) (!defined(MGX_ONLY_V) || MGX_ONLY_V == (v))
-#if MGX_TU_HAS(3)
 #define MGX_INST_V 3
 #include "mgx_fused_inst.hip"
-#undef MGX_INST_V
-#endif
-#if MGX_TU_HAS(5)
 #define MGX_INST_V 5
 #include "mgx_fused_inst.hip"
-#undef MGX_INST_V
-#endif
-#if MGX_TU_HAS(7)
 #define MGX_INST_V 7
 #include "mgx_fused_inst.hip"
-#undef MGX_INST_V
-#endif
-#if MGX_TU_HAS(9)
 #define MGX_INST_V 9
 #include "mgx_fused_inst.hip"
-#undef MGX_INST_V
-#endif
-#if MGX_TU_HAS(11)
 #define MGX_INST_V 11
 #include "mgx_fused_inst.hip"
-#undef MGX_INST_V
-#endif
-#if MGX_TU_HAS(13)
 #define MGX_INST_V 13
 #include "mgx_fused_inst.hip"
-#undef MGX_INST_V
-#endif
-#if MGX_TU_HAS(15)
 #define MGX_INST_V 15
 #include "mgx_fused_inst.hip"
-#undef MGX_INST_V
-#endif
 #endif
 
 namespace {
 
 using namespace mgx;
 using namespace mgx_fused;
-
-// mode 0: gen_obs, 1: one step, 2: rollout
-int launch(int mode, const KernelArgs &ka, int threads, int lds_bytes, int64_t nwg, hipStream_t stream, int *occupancy = nullptr);
 
 int g_last_hip_error = 0;
 
@@ -88,9 +63,21 @@ int g_span_nlaunch = 0;
 int g_span_next = 0;
 #endif
 
-int launch(int mode, const KernelArgs &ka_in, int threads, int lds_bytes, int64_t nwg, hipStream_t stream, int *occupancy) {
-    KernelArgs ka = ka_in;
-    lds_bytes += g_debug_lds_pad;
+// One launch, planned: what (form), with which arguments (ka) and geometry.  plan_launch() below fills it from (spec, batch, form);
+// the entry points add their pointers and hand it to launch().
+struct LaunchPlan {
+    LaunchForm form = LaunchForm::step();
+    KernelArgs ka{};
+    int threads = 0, lds_bytes = 0; int64_t nwg = 0;     // threads and LDS bytes per workgroup; workgroups
+    int waves_per_workgroup() const { return threads / 64; }
+    int64_t envs_per_wavefront() const { return (int64_t)ka.Gw * std::max(ka.ns, 1); }      // (resident shapes: all of its slices)
+    int64_t wavefronts() const { return (ka.batch + envs_per_wavefront() - 1) / envs_per_wavefront(); }   // ... that own envs
+    int64_t workgroups_for(int64_t waves) const { return (waves + waves_per_workgroup() - 1) / waves_per_workgroup(); }
+};
+
+// `occupancy`: query only -- the workgroups of the plan's instantiation that one CU holds; nothing is launched
+int launch(const LaunchPlan &lp, hipStream_t stream, int *occupancy = nullptr) {
+    KernelArgs ka = lp.ka;
 #if MGX_BOUNDS_CHECK
     if (!g_bounds) {                      // (normally made by mgx_abi_version(), which the binding calls when it loads the library)
         hipError_t eb = hipMalloc(reinterpret_cast<void **>(&g_bounds), 8);
@@ -101,7 +88,7 @@ int launch(int mode, const KernelArgs &ka_in, int threads, int lds_bytes, int64_
 #endif
 #if MGX_SPANS
     if (!occupancy) {
-        const long long nwaves = nwg * (threads / 64);
+        const long long nwaves = lp.nwg * lp.waves_per_workgroup();
         ka.span_base = g_span_next;
         if (g_span_nlaunch < kMaxSpanLaunches) {
             long long *r = g_span_launches[g_span_nlaunch++];
@@ -111,7 +98,7 @@ int launch(int mode, const KernelArgs &ka_in, int threads, int lds_bytes, int64_
     }
 #endif
     switch (ka.sp.view_size) {
-#define MGX_CASE(V) case V: return launch_v##V(mode, ka, threads, lds_bytes, nwg, stream, &g_last_hip_error, occupancy);
+#define MGX_CASE(V) case V: return launch_v##V(lp.form, ka, lp.threads, lp.lds_bytes + g_debug_lds_pad, lp.nwg, stream, &g_last_hip_error, occupancy);
 #if defined(MGX_ONLY_V)
 #define MGX_CASE_ONLY2(V) MGX_CASE(V)
 #define MGX_CASE_ONLY(V) MGX_CASE_ONLY2(V)
@@ -124,7 +111,7 @@ int launch(int mode, const KernelArgs &ka_in, int threads, int lds_bytes, int64_
     }
 }
 
-int check_spec(const MgxSpec *sp, int64_t batch, bool roll = false, bool one_hot = false, bool obs_only = false) {
+int check_spec(const MgxSpec *sp, int64_t batch, LaunchForm form) {
     if (!sp || batch < 0) return MGX_ERR_INVALID_ARGUMENT;
     if (sp->view_size < 3 || !(sp->view_size & 1)) return MGX_ERR_INVALID_ARGUMENT;   // agent.py:78-79
     if (sp->width < 3 || sp->height < 3 || sp->num_agents < 1 || sp->max_steps < 1) return MGX_ERR_INVALID_ARGUMENT;
@@ -136,11 +123,11 @@ int check_spec(const MgxSpec *sp, int64_t batch, bool roll = false, bool one_hot
     // output keep the 16-bit cells
     // (round 6: compact cells also take the hook-free STEP with one-hot output; gen_obs with one-hot output stays two launches)
     // (... and the hook-free rollout / persistent launch)
-    if ((sp->cell_bytes == 1 || sp->cell_bytes == 3) && (roll || one_hot)
-        && !(sp->cell_bytes == 1 && (one_hot != roll) && !obs_only && sp->env_kind == MGX_KIND_EMPTY))
+    if ((sp->cell_bytes == 1 || sp->cell_bytes == 3) && (form.roll() || form.one_hot)
+        && !(sp->cell_bytes == 1 && (form.one_hot != form.roll()) && !form.obs_only() && sp->env_kind == MGX_KIND_EMPTY))
         return MGX_ERR_UNSUPPORTED;
-    if (wave_lds_bytes(*sp, 1, roll, one_hot, obs_only) > kLdsPerCU) return MGX_ERR_UNSUPPORTED;   // one env must fit one CU's LDS (the
-                                                                                     // rollout carve is the larger one)
+    // one env must fit one CU's LDS (the rollout carve is the larger one)
+    if (wave_lds_bytes(*sp, 1, form, kGroup) > kLdsPerCU) return MGX_ERR_UNSUPPORTED;
     return MGX_OK;
 }
 
@@ -179,69 +166,139 @@ int resident_shape(const MgxSpec &sp, int64_t batch, bool persist) {
     return batch <= 65536 ? kShapeResident4 : kShapeResident1;
 }
 
-// `step_plain`: the launch is the plain one-step kernel (mode 1 without one-hot / generation): the only one the small-group
-// latency instantiations exist for (mgx_fused.h: has_small_groups)
-int fill_args(KernelArgs &ka, const MgxSpec *sp, int64_t batch, int &threads, int &lds_bytes, int64_t &nwg,
-              bool roll = false, bool one_hot = false, bool obs_only = false, bool step_plain = false, bool persist = false) {
-    ka.sp = *sp;
+// The geometry of a launch of `form` for (spec, batch) -- a spec check_spec(spec, batch, form) has accepted: envs per wavefront, the
+// wavefront's LDS carve, the instantiation family (ka.flags, ka.grp, the resident shape), wavefronts per workgroup, workgroups.
+int plan_launch(LaunchPlan &lp, const MgxSpec &sp, int64_t batch, LaunchForm form) {
+    KernelArgs &ka = lp.ka;
+    lp.form = form;
+    ka.sp = sp;
     ka.batch = batch;
-    ka.Gw = g_debug_G > 0 ? g_debug_G : choose_Gw(*sp, batch, roll, one_hot, obs_only);
-    const int max_gw = slots_per_wave(sp->view_size, roll || obs_only || sp->cell_bytes == 1) / sp->num_agents;
+    ka.Gw = g_debug_G > 0 ? g_debug_G : choose_Gw(sp, batch, form);
+    const int max_gw = form_slots(sp, form) / sp.num_agents;
     if (ka.Gw > max_gw) ka.Gw = max_gw;
     if (ka.Gw < 1) ka.Gw = 1;
-    while (ka.Gw > 1 && wave_lds_bytes(*sp, ka.Gw, roll, one_hot, obs_only) > kLdsPerCU) --ka.Gw;
+    while (ka.Gw > 1 && wave_lds_bytes(sp, ka.Gw, form, kGroup) > kLdsPerCU) --ka.Gw;
     ka.grp = kGroup;
     // latency regime: a wavefront that owns ONE small group of view slots (4 or 8) -- fewer slots of P2/P4/P5 on each wave's
     // instruction chain, more wavefronts per SIMD to run them side by side (mgx_fused.h: choose_group)
-    if (step_plain && has_small_groups(sp->view_size, 1, false, false) && sp->num_agents <= 8 && sp->cell_bytes != 1 && sp->cell_bytes != 3) {
-        const int g = g_debug_grp > 0 ? g_debug_grp : (g_debug_G > 0 ? kGroup : choose_group(*sp, batch));
-        if (g < kGroup && sp->num_agents <= g) { ka.grp = g; ka.Gw = g / sp->num_agents; }
+    if (form.plain_step() && has_small_groups(sp.view_size, form.family, form.one_hot, form.generate) && sp.num_agents <= 8
+        && sp.cell_bytes != 1 && sp.cell_bytes != 3) {
+        const int g = g_debug_grp > 0 ? g_debug_grp : (g_debug_G > 0 ? kGroup : choose_group(sp, batch));
+        if (g < kGroup && sp.num_agents <= g) { ka.grp = g; ka.Gw = g / sp.num_agents; }
     }
     ka.dbg = g_debug_skip;
     // a grid tensor beyond half of the 256 MiB Infinity Cache is streamed (nt tile loads): mgx_fused.h, P0.  (One of exactly half --
     // C5's 32768 compact 64x64 grids -- is still better left to the caches: 60.4 against 61.1-61.6 us with nt loads.)
-    ka.flags = (batch * (int64_t)sp->width * sp->height * grid_cell_bytes_of(*sp) > (int64_t)128 << 20) ? 1 : 0;
-    ka.vpw = slots_in_use(*sp, ka.Gw, roll || obs_only, ka.grp);
-    ka.inv_A = (65536 + sp->num_agents - 1) / sp->num_agents;
-    ka.wave_lds = wave_lds_bytes(*sp, ka.Gw, roll, one_hot, obs_only, ka.grp);
+    ka.flags = (batch * (int64_t)sp.width * sp.height * grid_cell_bytes_of(sp) > (int64_t)128 << 20) ? 1 : 0;
+    ka.vpw = slots_in_use(sp, ka.Gw, form, ka.grp);
+    ka.inv_A = (65536 + sp.num_agents - 1) / sp.num_agents;
+    ka.wave_lds = wave_lds_bytes(sp, ka.Gw, form, ka.grp);
     ka.ns = 0; ka.rshape = 0;
     // RESIDENT shapes of the rollout / persistent kernels (mgx_fused.h: kShapes[].ns > 0; round 6): at the batches where the 32-slot
     // rollout kernel no longer keeps every env on the chip, Empty-16x16 x 4 agents takes 64 view slots per wavefront and, beyond what
     // 12 such wavefronts per CU hold, two slices of 16 envs per wavefront (8 per CU: 65536 envs, C4, in 2048 wavefronts)
-    if (roll && !one_hot && !MGX_NO_FIXED_SHAPES && g_debug_G <= 0) {
-        const int rs = resident_shape(*sp, batch, persist);
+    if (form.roll() && !form.one_hot && !MGX_NO_FIXED_SHAPES && g_debug_G <= 0) {
+        const int rs = resident_shape(sp, batch, form.persist());
         if (rs > 0) {
             const FixedShape &f = kShapes[rs];
             ka.ns = f.ns; ka.rshape = rs; ka.Gw = f.Gw; ka.vpw = shape_slots(f);
             ka.wave_lds = shape_carve(f, true).total();
         }
     }
-    struct { int total; } p{ka.wave_lds};
     // wavefronts bundled per workgroup: ONE once the chip is full several times over -- single-wavefront workgroups pack a CU's
     // 160 KiB of LDS tightest and refill a CU one wavefront at a time (round 4, same box: C5 78.1 / 79.0 / 82.2 us for 1 / 2 / 4,
     // 262 144 envs of C4 59.2 / 60.5 / 60.5, 1 M envs 219.3 / 220.5 / 222.9); below that, fewer and larger workgroups launch
     // faster (9.9 vs 10.5 us at 4096 envs; C4's 4096 wavefronts: 18.9 for 4 against 19.2 for 1)
     // (... for the plain step's wavefronts, which hold more than 8 KiB of LDS each; the gen_obs kernel's small slices and the
     // one-hot step stay at 2: 1 M envs gen_obs 203 us for 1 against 190-193 for 2, fused one-hot step 1.03-1.06 ms against 0.99)
-    int wpb = ((batch + ka.Gw - 1) / ka.Gw >= 16384) ? ((p.total > 8192 && !one_hot && !obs_only) ? 1 : 2) : 4;
+    int wpb = ((batch + ka.Gw - 1) / ka.Gw >= 16384) ? ((ka.wave_lds > 8192 && !form.one_hot && !form.obs_only()) ? 1 : 2) : 4;
     if (ka.ns > 0) wpb = ka.rshape == kShapeResident4 ? 4 : 2;   // (resident shapes: 12 / 8 / 16 wavefronts per CU as 6 / 4 / 4 workgroups)
-    while (wpb > 1 && wpb * p.total > 64 * 1024) wpb >>= 1;
+    while (wpb > 1 && wpb * ka.wave_lds > 64 * 1024) wpb >>= 1;
     if (g_debug_wpb > 0) wpb = g_debug_wpb;
-    threads = 64 * wpb;
-    lds_bytes = wpb * p.total;
-    const int64_t nwaves = (batch + (int64_t)ka.Gw * std::max(ka.ns, 1) - 1) / ((int64_t)ka.Gw * std::max(ka.ns, 1));
+    lp.threads = 64 * wpb;
+    lp.lds_bytes = wpb * ka.wave_lds;
+    const int64_t nwaves = lp.wavefronts();
     // latency regime: LDS-DMA tile loads, 32 view slots with unpacked cell registers (mgx_fused.h: DMA instantiations)
     // (compact cells have no latency instantiation: their launches take the throughput kernel at any size)
-    if ((nwaves <= 2048 || ka.grp < kGroup) && !(ka.flags & 1) && ka.Gw * sp->num_agents <= kSlotsLatency && sp->cell_bytes != 1
-        && sp->cell_bytes != 3)
+    if ((nwaves <= 2048 || ka.grp < kGroup) && !(ka.flags & 1) && ka.Gw * sp.num_agents <= kSlotsLatency && sp.cell_bytes != 1
+        && sp.cell_bytes != 3)
         ka.flags |= 2;
     if (!(ka.flags & 2) && ka.grp < kGroup) return MGX_ERR_UNSUPPORTED;     // (cannot happen: small groups imply a small grid tensor)
-    nwg = (nwaves + wpb - 1) / wpb;
-    if (nwg > INT_MAX) return MGX_ERR_UNSUPPORTED;
+    lp.nwg = lp.workgroups_for(nwaves);
+    if (lp.nwg > INT_MAX) return MGX_ERR_UNSUPPORTED;
     return MGX_OK;
 }
 
 inline bool misaligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+
+// The state / input / output tensors of a stepping launch (include/mgx.h: MgxStepArgs): there where the spec needs them, aligned.
+// (the persistent launch takes its actions as granules: MgxPersistent)
+int check_step_pointers(const MgxSpec &sp, const MgxStepArgs &sa, LaunchForm form) {
+    if (!sa.grid || !sa.agents || !sa.step_count || (!sa.actions && !form.persist()) || !sa.obs || !sa.reward || !sa.terminated || !sa.truncated)
+        return MGX_ERR_INVALID_ARGUMENT;
+    if (sp.num_agents > 1 && !sa.rng) return MGX_ERR_INVALID_ARGUMENT;
+    if (sp.env_kind != MGX_KIND_EMPTY && !sa.aux) return MGX_ERR_INVALID_ARGUMENT;
+    if (misaligned(sa.grid, 16) || misaligned(sa.agents, 8) || misaligned(sa.obs, 16) || misaligned(sa.rng, 8)
+        || misaligned(sa.reward, 8) || misaligned(sa.step_count, 4) || misaligned(sa.err, 4) || misaligned(sa.aux, 16))
+        return MGX_ERR_INVALID_ARGUMENT;
+    return MGX_OK;
+}
+
+void bind_step_pointers(KernelArgs &ka, const MgxStepArgs &sa, LaunchForm form) {
+    ka.grid = reinterpret_cast<uint8_t *>(sa.grid); ka.agents = sa.agents; ka.rng = sa.rng; ka.step_count = sa.step_count;
+    if (!form.persist()) { ka.actions = sa.actions; ka.hook_order = sa.hook_order; }
+    ka.aux = sa.aux; ka.obs = sa.obs; ka.dir = sa.dir; ka.reward = sa.reward; ka.terminated = sa.terminated;
+    ka.truncated = sa.truncated; ka.err = sa.err;
+}
+
+// The fused auto-reset's layout pool (include/mgx.h: MgxAutoReset)
+int check_auto_reset(const MgxSpec &sp, const MgxAutoReset &ar) {
+    if (ar.pool_size < 1 || ar.first_env < 0 || !ar.pool_grid || !ar.pool_agents || !ar.episode) return MGX_ERR_INVALID_ARGUMENT;
+    if (sp.env_kind != MGX_KIND_EMPTY && !ar.pool_aux) return MGX_ERR_INVALID_ARGUMENT;
+    if (misaligned(ar.pool_agents, 8) || misaligned(ar.pool_aux, 16) || misaligned(ar.episode, 4)) return MGX_ERR_INVALID_ARGUMENT;
+    return MGX_OK;
+}
+
+// A non-null ka.pool_grid is what selects the instantiations WITH the fused auto-reset (mgx_fused.h: launch_mode, `ar`).
+// `occupancy`: the plan is for an occupancy query, which checks no pointer and launches nothing but must ask about the kernel the
+// launch will run: a null pool_grid is stood in for by the spec's address.
+void bind_auto_reset(KernelArgs &ka, const MgxSpec *spec, const MgxAutoReset &ar, const int *occupancy = nullptr) {
+    ka.pool_size = ar.pool_size; ka.first_env = ar.first_env;
+    ka.pool_magic = ar.pool_size > 1 ? ~0ull / (uint64_t)ar.pool_size + 1ull : 0ull;
+    ka.pool_grid = reinterpret_cast<const uint8_t *>(ar.pool_grid);
+    ka.pool_agents = ar.pool_agents; ka.pool_aux = ar.pool_aux; ka.episode = ar.episode; ka.was_reset = ar.was_reset;
+    if (occupancy && !ka.pool_grid) ka.pool_grid = reinterpret_cast<const uint8_t *>(spec);
+}
+
+// Staged generation (include/mgx.h: MgxGenStage), for the generated step and mgx_stage_generate: the slots are there (and A > 1) ...
+bool stage_present(const MgxSpec &sp, const MgxGenStage &st) {
+    return st.grid && st.agents && st.words && st.tag && (st.aux || sp.env_kind == MGX_KIND_EMPTY) && sp.num_agents > 1;
+}
+bool stage_misaligned(const MgxGenStage &st) {
+    return misaligned(st.grid, 4) || misaligned(st.agents, 8) || misaligned(st.aux, 16) || misaligned(st.words, 8) || misaligned(st.tag, 16);
+}
+// ... a generator wavefront's 64 lanes fit the step's LDS slice
+bool stage_fits(const LaunchPlan &lp) { return lp.ka.wave_lds >= 128 * lp.ka.sp.num_agents; }
+// ... candidates (ABI 10): only with the generator launches between the steps, only what the generator kind offers
+bool stage_candidates_ok(const MgxLayoutGen *gen) {
+    const MgxGenStage &st = gen->stage;
+    return st.candidates == 0 || (st.candidates > 0 && st.external == 2 && st.candidates == mgx_gen::stage_candidates(gen));
+}
+// ... and what device-side generation asks of the spec
+int check_generator(const MgxSpec *spec, const MgxLayoutGen *gen) {
+    if (spec->width > 254 || spec->height > 254) return MGX_ERR_UNSUPPORTED;
+    return mgx_gen::check_layout_gen(spec, gen);
+}
+
+int device_cu_count(int &cus) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess) e = hipGetDeviceProperties(&prop, dev);
+    if (e != hipSuccess) return hip_failed(e);
+    cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 1;
+    return MGX_OK;
+}
 
 // runtime-compiled shape instantiations (mgx_shape_register); never removed: a launch may hold a pointer into the vector's elements,
 // so they live in a list of stable nodes
@@ -358,53 +415,53 @@ int mgx_debug_read_stamps(unsigned long long *out64, long long wave) {   // read
 #endif
 
 int mgx_launch_info(const MgxSpec *spec, int64_t batch, MgxLaunchInfo *out) {
-    int rc = check_spec(spec, batch);
+    const LaunchForm form = LaunchForm::step();
+    int rc = check_spec(spec, batch, form);
     if (rc) return rc;
     if (!out) return MGX_ERR_INVALID_ARGUMENT;
-    KernelArgs ka{};
-    int threads = 0, lds = 0; int64_t nwg = 0;
-    rc = fill_args(ka, spec, batch, threads, lds, nwg, false, false, false, true);     // (the plain step's geometry)
+    LaunchPlan lp;
+    rc = plan_launch(lp, *spec, batch, form);
     if (rc) return rc;
-    out->envs_per_wavefront = ka.Gw;
-    out->envs_per_workgroup = ka.Gw * (threads / 64);
-    out->threads_per_workgroup = threads;
-    out->workgroups = (int32_t)nwg;
-    out->lds_bytes = lds;
-    out->slots_per_group = ka.grp;
-    out->fixed_shape = match_fixed_shape(ka, spec->env_kind != MGX_KIND_EMPTY);
-    if (!out->fixed_shape && jit_shape_lookup(ka, spec->env_kind != MGX_KIND_EMPTY)) out->fixed_shape = MGX_SHAPE_RUNTIME_COMPILED;
+    out->envs_per_wavefront = lp.ka.Gw;
+    out->envs_per_workgroup = lp.ka.Gw * lp.waves_per_workgroup();
+    out->threads_per_workgroup = lp.threads;
+    out->workgroups = (int32_t)lp.nwg;
+    out->lds_bytes = lp.lds_bytes;
+    out->slots_per_group = lp.ka.grp;
+    out->fixed_shape = match_fixed_shape(lp.ka, spec->env_kind != MGX_KIND_EMPTY);
+    if (!out->fixed_shape && jit_shape_lookup(lp.ka, spec->env_kind != MGX_KIND_EMPTY)) out->fixed_shape = MGX_SHAPE_RUNTIME_COMPILED;
     return MGX_OK;
 }
 
 int mgx_rollout_info(const MgxSpec *spec, int64_t batch, int32_t persistent, MgxRolloutInfo *out) {
-    int rc = check_spec(spec, batch, true, false);
+    const LaunchForm form = persistent ? LaunchForm::persistent() : LaunchForm::rollout();
+    int rc = check_spec(spec, batch, form);
     if (rc) return rc;
     if (!out) return MGX_ERR_INVALID_ARGUMENT;
-    KernelArgs ka{};
-    int threads = 0, lds = 0; int64_t nwg = 0;
-    rc = fill_args(ka, spec, batch, threads, lds, nwg, true, false, false, false, persistent != 0);
+    LaunchPlan lp;
+    rc = plan_launch(lp, *spec, batch, form);
     if (rc) return rc;
-    const int64_t epw = (int64_t)ka.Gw * std::max(ka.ns, 1);
-    out->envs_per_slice = ka.Gw;
-    out->slices = std::max(ka.ns, 1);
-    out->wavefronts = (int32_t)((batch + epw - 1) / epw);
-    out->threads_per_workgroup = threads;
-    out->workgroups = (int32_t)nwg;
-    out->lds_bytes = lds;
-    out->resident_shape = match_resident_shape(ka, spec->env_kind != MGX_KIND_EMPTY);
+    out->envs_per_slice = lp.ka.Gw;
+    out->slices = std::max(lp.ka.ns, 1);
+    out->wavefronts = (int32_t)lp.wavefronts();
+    out->threads_per_workgroup = lp.threads;
+    out->workgroups = (int32_t)lp.nwg;
+    out->lds_bytes = lp.lds_bytes;
+    out->resident_shape = match_resident_shape(lp.ka, spec->env_kind != MGX_KIND_EMPTY);
     return MGX_OK;
 }
 
 // ---- runtime-compiled shape specialisation (include/mgx.h: MgxShapeKey) -------------------------------------------------
 int mgx_shape_key(const MgxSpec *spec, int64_t batch, MgxShapeKey *key) {
-    int rc = check_spec(spec, batch);
+    const LaunchForm form = LaunchForm::step();
+    int rc = check_spec(spec, batch, form);
     if (rc) return rc;
     if (!key || batch < 1) return MGX_ERR_INVALID_ARGUMENT;
     if (spec->cell_bytes == 1 || spec->cell_bytes == 3) return MGX_ERR_UNSUPPORTED;            // (runtime-compiled shapes: 16-bit cells)
-    KernelArgs ka{};
-    int threads = 0, lds = 0; int64_t nwg = 0;
-    rc = fill_args(ka, spec, batch, threads, lds, nwg, false, false, false, true);
+    LaunchPlan lp;
+    rc = plan_launch(lp, *spec, batch, form);
     if (rc) return rc;
+    const KernelArgs &ka = lp.ka;
     const bool hooks = spec->env_kind != MGX_KIND_EMPTY;
     key->width = spec->width; key->height = spec->height; key->num_agents = spec->num_agents; key->envs_per_wavefront = ka.Gw;
     key->hooks = hooks ? 1 : 0; key->view_size = spec->view_size; key->dma = (ka.flags & 2) ? 1 : 0; key->stream = (ka.flags & 1) ? 1 : 0;
@@ -449,21 +506,22 @@ int mgx_shape_register(const MgxShapeKey *key, const void *code_object, size_t b
 
 static int gen_obs_common(bool one_hot, const MgxSpec *spec, int64_t batch, const MgxCell *grid, const uint8_t *agents,
                           uint8_t *obs, uint8_t *dir, void *stream) {
-    int rc = check_spec(spec, batch, false, one_hot, true);
+    const LaunchForm form = LaunchForm::gen_obs().with_one_hot(one_hot);
+    int rc = check_spec(spec, batch, form);
     if (rc) return rc;
     if (batch == 0) return MGX_OK;
     if (!grid || !agents || !obs) return MGX_ERR_INVALID_ARGUMENT;
     if (misaligned(grid, 16) || misaligned(agents, 8) || misaligned(obs, 16)) return MGX_ERR_INVALID_ARGUMENT;
-    KernelArgs ka{};
-    int threads = 0, lds = 0; int64_t nwg = 0;
-    rc = fill_args(ka, spec, batch, threads, lds, nwg, false, one_hot, true);
+    LaunchPlan lp;
+    rc = plan_launch(lp, *spec, batch, form);
     if (rc) return rc;
+    KernelArgs &ka = lp.ka;
     ka.grid = reinterpret_cast<uint8_t *>(const_cast<MgxCell *>(grid));
     ka.agents = const_cast<uint8_t *>(agents);
     ka.obs = obs;
     ka.dir = dir;
     ka.T = 1;
-    return launch(one_hot ? 4 : 0, ka, threads, lds, nwg, static_cast<hipStream_t>(stream));
+    return launch(lp, static_cast<hipStream_t>(stream));
 }
 
 int mgx_gen_obs(const MgxSpec *spec, int64_t batch, const MgxCell *grid, const uint8_t *agents,
@@ -481,45 +539,27 @@ static int step_common(const MgxSpec *spec, int64_t batch, const MgxStepArgs &sa
     const bool roll = sa.steps != 1, one_hot = sa.one_hot != 0;
     const MgxAutoReset *ar = sa.auto_reset;
     const MgxLayoutGen *gen = sa.generate;
-    int rc = check_spec(spec, batch, roll, one_hot);
+    // (steps = T with generation is T launches of the one-step form, below: until then it is checked and planned as the rollout)
+    const LaunchForm form = roll ? LaunchForm::rollout().with_one_hot(one_hot)
+                                 : LaunchForm::step().with_one_hot(one_hot).with_generate(gen != nullptr);
+    int rc = check_spec(spec, batch, form);
     if (rc) return rc;
     if (sa.steps < 0) return MGX_ERR_INVALID_ARGUMENT;
     if (batch == 0 || sa.steps == 0) return MGX_OK;
     if (!occupancy) {
-        if (!sa.grid || !sa.agents || !sa.step_count || !sa.actions || !sa.obs || !sa.reward || !sa.terminated || !sa.truncated)
-            return MGX_ERR_INVALID_ARGUMENT;
-        if (spec->num_agents > 1 && !sa.rng) return MGX_ERR_INVALID_ARGUMENT;
-        if (spec->env_kind != MGX_KIND_EMPTY && !sa.aux) return MGX_ERR_INVALID_ARGUMENT;
-        if (misaligned(sa.grid, 16) || misaligned(sa.agents, 8) || misaligned(sa.obs, 16) || misaligned(sa.rng, 8)
-            || misaligned(sa.reward, 8) || misaligned(sa.step_count, 4) || misaligned(sa.err, 4) || misaligned(sa.aux, 16))
-            return MGX_ERR_INVALID_ARGUMENT;
+        rc = check_step_pointers(*spec, sa, form);
+        if (!rc && ar) rc = check_auto_reset(*spec, *ar);
+        if (rc) return rc;
     }
-    KernelArgs ka{};
-    if (ar) {
-        if (!occupancy) {
-            if (ar->pool_size < 1 || ar->first_env < 0 || !ar->pool_grid || !ar->pool_agents || !ar->episode)
-                return MGX_ERR_INVALID_ARGUMENT;
-            if (spec->env_kind != MGX_KIND_EMPTY && !ar->pool_aux) return MGX_ERR_INVALID_ARGUMENT;
-            if (misaligned(ar->pool_agents, 8) || misaligned(ar->pool_aux, 16) || misaligned(ar->episode, 4))
-                return MGX_ERR_INVALID_ARGUMENT;
-        }
-        ka.pool_size = ar->pool_size; ka.first_env = ar->first_env;
-        ka.pool_magic = ar->pool_size > 1 ? ~0ull / (uint64_t)ar->pool_size + 1ull : 0ull; ka.pool_grid = reinterpret_cast<const uint8_t *>(ar->pool_grid);
-        ka.pool_agents = ar->pool_agents; ka.pool_aux = ar->pool_aux; ka.episode = ar->episode;
-        ka.was_reset = ar->was_reset;
-        if (occupancy && !ka.pool_grid) ka.pool_grid = reinterpret_cast<const uint8_t *>(spec);   // (selects the AR instantiation)
-    }
-    int threads = 0, lds = 0; int64_t nwg = 0;
-    rc = fill_args(ka, spec, batch, threads, lds, nwg, roll, one_hot, false, !roll && !one_hot && !gen);
+    LaunchPlan lp;
+    rc = plan_launch(lp, *spec, batch, form);
     if (rc) return rc;
-    ka.grid = reinterpret_cast<uint8_t *>(sa.grid); ka.agents = sa.agents; ka.rng = sa.rng; ka.step_count = sa.step_count;
-    ka.actions = sa.actions; ka.hook_order = sa.hook_order;
-    ka.aux = sa.aux; ka.obs = sa.obs; ka.dir = sa.dir; ka.reward = sa.reward; ka.terminated = sa.terminated;
-    ka.truncated = sa.truncated; ka.err = sa.err;
+    KernelArgs &ka = lp.ka;
+    if (ar) bind_auto_reset(ka, spec, *ar, occupancy);
+    bind_step_pointers(ka, sa, form);
     ka.grid_bad = spec->cell_bytes == 3 ? sa.grid_bad : nullptr;
     if (misaligned(ka.grid_bad, 4)) return MGX_ERR_INVALID_ARGUMENT;
     ka.T = roll ? sa.steps : 1;
-    int mode = (roll ? 2 : 1) | (one_hot ? 4 : 0);
     if (gen) {
         if (ar) return MGX_ERR_INVALID_ARGUMENT;
         if (spec->cell_bytes == 1 || spec->cell_bytes == 3) return MGX_ERR_UNSUPPORTED;        // (device-side generation writes 16-bit cells)
@@ -562,38 +602,27 @@ static int step_common(const MgxSpec *spec, int64_t batch, const MgxStepArgs &sa
             if (!gen->blank || !gen->gen_state || !sa.episode || !sa.rng) return MGX_ERR_INVALID_ARGUMENT;
             if (misaligned(gen->gen_state, 8) || misaligned(sa.episode, 4)) return MGX_ERR_INVALID_ARGUMENT;
         }
-        if (spec->width > 254 || spec->height > 254) return MGX_ERR_UNSUPPORTED;
-        rc = mgx_gen::check_layout_gen(spec, gen);
+        rc = check_generator(spec, gen);
         if (rc) return rc;
         ka.gen = *gen; ka.episode = sa.episode; ka.was_reset = sa.was_reset;
         ka.gen_first_wg = INT64_MAX;
         // staged generation (include/mgx.h: MgxGenStage): generator wavefronts behind the step's own workgroups, one lane per env
         MgxGenStage &st = ka.gen.stage;
-        const bool staged = st.grid && st.agents && st.words && st.tag && (st.aux || spec->env_kind == MGX_KIND_EMPTY)
-                            && spec->num_agents > 1 && ka.wave_lds >= 128 * spec->num_agents;
-        if (staged) {
-            if (misaligned(st.grid, 4) || misaligned(st.agents, 8) || misaligned(st.aux, 16) || misaligned(st.words, 8)
-                || misaligned(st.tag, 16))
-                return MGX_ERR_INVALID_ARGUMENT;
+        if (stage_present(*spec, st) && stage_fits(lp)) {
+            if (stage_misaligned(st) || !stage_candidates_ok(gen)) return MGX_ERR_INVALID_ARGUMENT;
             if (st.lead < 0 || st.lead >= spec->max_steps) return MGX_ERR_INVALID_ARGUMENT;
             if (st.lead < 2) st.lead = 2;
             if (st.external < 0 || st.external > 2) return MGX_ERR_INVALID_ARGUMENT;
-            // candidates (ABI 10): only with the generator launches between the steps, only what the generator kind offers
-            if (st.candidates < 0 || (st.candidates > 0 && (st.external != 2 || st.candidates != mgx_gen::stage_candidates(gen))))
-                return MGX_ERR_INVALID_ARGUMENT;
             if (!st.external) {                                  // generator wavefronts behind the step's own workgroups
-                const int wpb = threads / 64;
-                const int64_t gen_waves = (batch + 63) / 64;
-                ka.gen_first_wg = nwg;
-                nwg += (gen_waves + wpb - 1) / wpb;
-                if (nwg > INT_MAX) return MGX_ERR_UNSUPPORTED;
+                ka.gen_first_wg = lp.nwg;
+                lp.nwg += lp.workgroups_for((batch + 63) / 64);
+                if (lp.nwg > INT_MAX) return MGX_ERR_UNSUPPORTED;
             }
         } else {
             st = MgxGenStage{};
         }
-        mode |= 8;
     }
-    return launch(mode, ka, threads, lds, nwg, static_cast<hipStream_t>(stream), occupancy);
+    return launch(lp, static_cast<hipStream_t>(stream), occupancy);
 }
 
 static MgxStepArgs step_args(MgxCell *grid, uint8_t *agents, uint64_t *rng, int32_t *step_count, const int8_t *actions,
@@ -623,7 +652,7 @@ int mgx_rollout(const MgxSpec *spec, int64_t batch, int32_t steps, MgxCell *grid
                 uint8_t *obs, uint8_t *dir, double *reward, uint8_t *terminated, uint8_t *truncated,
                 int32_t *err, void *stream) {
     MgxStepArgs sa = step_args(grid, agents, rng, step_count, actions, aux, obs, dir, reward, terminated, truncated, err);
-    if (steps == 0) return check_spec(spec, batch, true);
+    if (steps == 0) return check_spec(spec, batch, LaunchForm::rollout());
     if (steps < 0) return MGX_ERR_INVALID_ARGUMENT;
     if (steps == 1) return step_common(spec, batch, sa, stream);          // (one step IS the step kernel: same results)
     sa.steps = steps;
@@ -647,7 +676,7 @@ int mgx_rollout_autoreset(const MgxSpec *spec, int64_t batch, int32_t steps, con
     if (!ar || steps < 0) return MGX_ERR_INVALID_ARGUMENT;
     MgxStepArgs sa = step_args(grid, agents, rng, step_count, actions, aux, obs, dir, reward, terminated, truncated, err);
     sa.auto_reset = ar;
-    if (steps == 0) return check_spec(spec, batch, true);
+    if (steps == 0) return check_spec(spec, batch, LaunchForm::rollout());
     sa.steps = steps;
     return step_common(spec, batch, sa, stream);
 }
@@ -663,25 +692,23 @@ int mgx_step_one_hot(const MgxSpec *spec, int64_t batch, const MgxAutoReset *ar,
 
 int mgx_stage_generate(const MgxSpec *spec, int64_t batch, const MgxLayoutGen *gen, const uint64_t *rng, const int32_t *episode,
                        void *stream) {
-    int rc = check_spec(spec, batch);
+    const LaunchForm form = LaunchForm::step().with_generate();      // (the generated step's carve: its LDS slice)
+    int rc = check_spec(spec, batch, form);
     if (rc) return rc;
     if (batch == 0) return MGX_OK;
     if (spec->cell_bytes == 1 || spec->cell_bytes == 3) return MGX_ERR_UNSUPPORTED;
-    if (!gen || !rng || !episode || !gen->blank || !gen->gen_state) return MGX_ERR_INVALID_ARGUMENT;
-    const MgxGenStage &gs = gen->stage;
-    if (!gs.grid || !gs.agents || !gs.words || !gs.tag || (!gs.aux && spec->env_kind != MGX_KIND_EMPTY) || spec->num_agents < 2)
+    if (!gen || !rng || !episode || !gen->blank || !gen->gen_state || !stage_present(*spec, gen->stage)) return MGX_ERR_INVALID_ARGUMENT;
+    if (stage_misaligned(gen->stage) || misaligned(gen->gen_state, 8) || misaligned(rng, 8) || misaligned(episode, 4))
         return MGX_ERR_INVALID_ARGUMENT;
-    if (misaligned(gs.grid, 4) || misaligned(gs.agents, 8) || misaligned(gs.aux, 16) || misaligned(gs.words, 8) || misaligned(gs.tag, 16)
-        || misaligned(gen->gen_state, 8) || misaligned(rng, 8) || misaligned(episode, 4))
-        return MGX_ERR_INVALID_ARGUMENT;
-    if (spec->width > 254 || spec->height > 254) return MGX_ERR_UNSUPPORTED;
-    rc = mgx_gen::check_layout_gen(spec, gen);
+    rc = check_generator(spec, gen);
     if (rc) return rc;
-    KernelArgs ka{};
-    int threads = 0, lds = 0; int64_t nwg = 0;
-    rc = fill_args(ka, spec, batch, threads, lds, nwg, false, false, false, false);     // (the generated step's carve: its LDS slice)
+    LaunchPlan lp;
+    rc = plan_launch(lp, *spec, batch, form);
     if (rc) return rc;
-    if (ka.wave_lds < 128 * spec->num_agents) return MGX_ERR_UNSUPPORTED;
+    if (!stage_fits(lp)) return MGX_ERR_UNSUPPORTED;
+    if (!stage_candidates_ok(gen)) return MGX_ERR_INVALID_ARGUMENT;
+    if (gen->stage.candidates > 0) return mgx_internal_stage_candidates(spec, batch, gen, episode, stream);   // (a kernel of its own: mgx_layout_gen.hip)
+    KernelArgs &ka = lp.ka;
     ka.rng = const_cast<uint64_t *>(rng);
     ka.episode = const_cast<int32_t *>(episode);
     ka.gen = *gen;
@@ -689,14 +716,9 @@ int mgx_stage_generate(const MgxSpec *spec, int64_t batch, const MgxLayoutGen *g
     ka.gen.stage.lead = ka.gen.stage.lead < 2 ? 2 : ka.gen.stage.lead;
     ka.gen_first_wg = 0;                                 // every workgroup of this launch is a generator workgroup
     ka.T = 1;
-    if (gs.candidates < 0 || (gs.candidates > 0 && (gs.external != 2 || gs.candidates != mgx_gen::stage_candidates(gen))))
-        return MGX_ERR_INVALID_ARGUMENT;
-    if (gs.candidates > 0) return mgx_internal_stage_candidates(spec, batch, gen, episode, stream);   // (a kernel of its own: mgx_layout_gen.hip)
-    const int wpb = threads / 64;
-    const int64_t gen_waves = (batch + 63) / 64;
-    nwg = (gen_waves + wpb - 1) / wpb;
-    if (nwg > INT_MAX) return MGX_ERR_UNSUPPORTED;
-    return launch(1 | 8, ka, threads, lds, nwg, static_cast<hipStream_t>(stream));
+    lp.nwg = lp.workgroups_for((batch + 63) / 64);
+    if (lp.nwg > INT_MAX) return MGX_ERR_UNSUPPORTED;
+    return launch(lp, static_cast<hipStream_t>(stream));
 }
 
 int mgx_step_generate(const MgxSpec *spec, int64_t batch, const MgxLayoutGen *gen, MgxCell *grid, uint8_t *agents,
@@ -727,24 +749,19 @@ int mgx_sub_shards(const MgxSpec *spec, int64_t batch, const MgxStepArgs *args, 
     MgxStepArgs sa{};
     if (args) sa = *args; else sa.steps = 1;
     if (sa.steps != 1) return MGX_OK;                                  // rollouts: one launch, nothing to chain
-    int rc = check_spec(spec, batch, false, sa.one_hot != 0);
+    const LaunchForm form = LaunchForm::step().with_one_hot(sa.one_hot != 0).with_generate(sa.generate != nullptr);
+    int rc = check_spec(spec, batch, form);
     if (rc) return rc;
     if (batch == 0) return MGX_OK;
-    int dev = 0;
-    hipDeviceProp_t prop;
-    {
-        hipError_t ed = hipGetDevice(&dev);
-        if (ed == hipSuccess) ed = hipGetDeviceProperties(&prop, dev);
-        if (ed != hipSuccess) return hip_failed(ed);
-    }
-    const int cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 1;
-    const int simds = 4 * cus;                                         // CDNA: four SIMDs per CU
-    KernelArgs ka{};
-    int threads = 0, lds = 0; int64_t nwg = 0;
-    rc = fill_args(ka, spec, batch, threads, lds, nwg, false, sa.one_hot != 0, false, !sa.one_hot && !sa.generate);
+    int cus = 0;
+    rc = device_cu_count(cus);
     if (rc) return rc;
-    if (ka.grp < kGroup) return MGX_OK;                                // the latency regime: one launch
-    const int64_t nwaves = (batch + ka.Gw - 1) / ka.Gw;
+    const int simds = 4 * cus;                                         // CDNA: four SIMDs per CU
+    LaunchPlan lp;
+    rc = plan_launch(lp, *spec, batch, form);
+    if (rc) return rc;
+    if (lp.ka.grp < kGroup) return MGX_OK;                             // the latency regime: one launch
+    const int64_t nwaves = lp.wavefronts();
     // below two wavefronts per SIMD (or a view per lane of two waves per SIMD) a launch is a lone wave's instruction chain:
     // splitting it only adds launches
     if (nwaves < 2 * (int64_t)simds || batch * spec->num_agents < 64 * (int64_t)simds) return MGX_OK;
@@ -821,87 +838,65 @@ int mgx_step_chains(const MgxSpec *spec, int64_t batch, const MgxStepArgs *args,
 
 // ---- persistent stepping (include/mgx.h: MgxPersistent) --------------------------------------------------------------
 // Geometry + residency of the persistent launch: the rollout kernel's carve, every wavefront resident at once.
-static int persistent_geometry(const MgxSpec *spec, int64_t batch, const MgxStepArgs *args, KernelArgs &ka, int &threads, int &lds,
-                               int64_t &nwg) {
-    int rc = check_spec(spec, batch, true, false);
+static int persistent_geometry(const MgxSpec *spec, int64_t batch, const MgxStepArgs *args, LaunchPlan &lp) {
+    const LaunchForm form = LaunchForm::persistent();
+    int rc = check_spec(spec, batch, form);
     if (rc) return rc;
     if (batch < 1) return MGX_ERR_INVALID_ARGUMENT;
     if (args && (args->one_hot || args->generate || args->hook_order)) return MGX_ERR_UNSUPPORTED;
-    const MgxAutoReset *ar = args ? args->auto_reset : nullptr;
-    if (ar) ka.pool_grid = reinterpret_cast<const uint8_t *>(ar->pool_grid ? ar->pool_grid : reinterpret_cast<const MgxCell *>(spec));
-    rc = fill_args(ka, spec, batch, threads, lds, nwg, true, false, false, false, true);
+    rc = plan_launch(lp, *spec, batch, form);
     if (rc) return rc;
-    ka.T = 1;
-    int occ = 0;
-    rc = launch(3, ka, threads, lds, nwg, nullptr, &occ);              // workgroups of THIS instantiation one CU holds
+    int occ = 0, cus = 0;
+    if (args && args->auto_reset) bind_auto_reset(lp.ka, spec, *args->auto_reset, &occ);   // (not checked yet: as the query's)
+    lp.ka.T = 1;
+    rc = launch(lp, nullptr, &occ);                                    // workgroups of THIS instantiation one CU holds
+    if (!rc) rc = device_cu_count(cus);
     if (rc) return rc;
-    int dev = 0;
-    hipDeviceProp_t prop;
-    {
-        hipError_t ed = hipGetDevice(&dev);
-        if (ed == hipSuccess) ed = hipGetDeviceProperties(&prop, dev);
-        if (ed != hipSuccess) return hip_failed(ed);
-    }
     // (the occupancy API is optimistic for kernels with many SGPRs -- guide: "Residency and cooperative launch" -- and a
     // workgroup that is admitted but not resident would hang the hand-shake until its timeout: at most 4 per CU are counted)
-    const int64_t resident = (int64_t)(prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 1) * std::min(occ, 4);
-    if (nwg > resident) return MGX_ERR_UNSUPPORTED;
+    if (lp.nwg > (int64_t)cus * std::min(occ, 4)) return MGX_ERR_UNSUPPORTED;
     return MGX_OK;
 }
 
 int mgx_persistent_waves(const MgxSpec *spec, int64_t batch, const MgxStepArgs *args, int32_t *waves) {
     if (!waves) return MGX_ERR_INVALID_ARGUMENT;
-    KernelArgs ka{};
-    int threads = 0, lds = 0; int64_t nwg = 0;
-    const int rc = persistent_geometry(spec, batch, args, ka, threads, lds, nwg);
+    LaunchPlan lp;
+    const int rc = persistent_geometry(spec, batch, args, lp);
     if (rc) return rc;
-    const int64_t epw = (int64_t)ka.Gw * std::max(ka.ns, 1);     // envs per wavefront (resident shapes: all of its slices)
-    *waves = (int32_t)((batch + epw - 1) / epw);            // (the wavefronts that own envs: the ones that publish a flag)
+    *waves = (int32_t)lp.wavefronts();                     // (the wavefronts that own envs: the ones that publish a flag)
     return MGX_OK;
 }
 
 int mgx_step_persistent(const MgxSpec *spec, int64_t batch, const MgxStepArgs *args, const MgxPersistent *p, void *stream) {
     if (!args || !p) return MGX_ERR_INVALID_ARGUMENT;
     const MgxStepArgs &sa = *args;
-    KernelArgs ka{};
-    int threads = 0, lds = 0; int64_t nwg = 0;
-    int rc = persistent_geometry(spec, batch, args, ka, threads, lds, nwg);
+    LaunchPlan lp;
+    int rc = persistent_geometry(spec, batch, args, lp);
+    if (!rc) rc = check_step_pointers(*spec, sa, lp.form);
     if (rc) return rc;
-    if (!sa.grid || !sa.agents || !sa.step_count || !sa.obs || !sa.reward || !sa.terminated || !sa.truncated)
-        return MGX_ERR_INVALID_ARGUMENT;
-    if (spec->num_agents > 1 && !sa.rng) return MGX_ERR_INVALID_ARGUMENT;
-    if (spec->env_kind != MGX_KIND_EMPTY && !sa.aux) return MGX_ERR_INVALID_ARGUMENT;
-    if (misaligned(sa.grid, 16) || misaligned(sa.agents, 8) || misaligned(sa.obs, 16) || misaligned(sa.rng, 8)
-        || misaligned(sa.reward, 8) || misaligned(sa.step_count, 4) || misaligned(sa.err, 4) || misaligned(sa.aux, 16))
-        return MGX_ERR_INVALID_ARGUMENT;
     if (!p->action_granules || !p->done || !p->ctrl || p->max_steps < 1 || p->timeout_ms < 1 || p->timeout_ms > 30000
         || misaligned(p->action_granules, 8) || misaligned(p->done, 4) || misaligned(p->ctrl, 4))
         return MGX_ERR_INVALID_ARGUMENT;
+    KernelArgs &ka = lp.ka;
     if (const MgxAutoReset *ar = sa.auto_reset) {
-        if (ar->pool_size < 1 || ar->first_env < 0 || !ar->pool_grid || !ar->pool_agents || !ar->episode) return MGX_ERR_INVALID_ARGUMENT;
-        if (spec->env_kind != MGX_KIND_EMPTY && !ar->pool_aux) return MGX_ERR_INVALID_ARGUMENT;
-        if (misaligned(ar->pool_agents, 8) || misaligned(ar->pool_aux, 16) || misaligned(ar->episode, 4)) return MGX_ERR_INVALID_ARGUMENT;
-        ka.pool_size = ar->pool_size; ka.first_env = ar->first_env;
-        ka.pool_magic = ar->pool_size > 1 ? ~0ull / (uint64_t)ar->pool_size + 1ull : 0ull;
-        ka.pool_grid = reinterpret_cast<const uint8_t *>(ar->pool_grid);
-        ka.pool_agents = ar->pool_agents; ka.pool_aux = ar->pool_aux; ka.episode = ar->episode; ka.was_reset = ar->was_reset;
+        rc = check_auto_reset(*spec, *ar);
+        if (rc) return rc;
+        bind_auto_reset(ka, spec, *ar);
     }
-    ka.grid = reinterpret_cast<uint8_t *>(sa.grid); ka.agents = sa.agents; ka.rng = sa.rng; ka.step_count = sa.step_count;
-    ka.aux = sa.aux; ka.obs = sa.obs; ka.dir = sa.dir; ka.reward = sa.reward; ka.terminated = sa.terminated;
-    ka.truncated = sa.truncated; ka.err = sa.err;
+    bind_step_pointers(ka, sa, lp.form);
     ka.T = p->max_steps;
     ka.granules = p->action_granules; ka.done = p->done; ka.pctrl = p->ctrl;
     ka.timeout_ticks = (uint32_t)p->timeout_ms * 100000u;              // s_memrealtime: 100 MHz
 #if MGX_SPANS
     {   // (spans build: one record per (step, wavefront) of this launch instead of one per wavefront)
-        const long long nrec = (long long)nwg * (threads / 64) * std::min<long long>(p->max_steps, 4096);
+        const long long nrec = (long long)lp.nwg * lp.waves_per_workgroup() * std::min<long long>(p->max_steps, 4096);
         const int base = g_span_next;
-        rc = launch(3, ka, threads, lds, nwg, static_cast<hipStream_t>(stream));
+        rc = launch(lp, static_cast<hipStream_t>(stream));
         g_span_next = (int)std::min<long long>((long long)kSpanCap, base + nrec);
         return rc;
     }
 #endif
-    return launch(3, ka, threads, lds, nwg, static_cast<hipStream_t>(stream));
+    return launch(lp, static_cast<hipStream_t>(stream));
 }
 
 void mgx_internal_set_hip_error(int e) { g_last_hip_error = e; }   // (not in include/mgx.h: mgx_layout_gen.hip / mgx_aux.hip report
