@@ -331,6 +331,7 @@ def main():
     record_random_states()   # (constructs no registered env: every make_env() above keeps its construction seed)
     record_resets()          # (likewise; both generators' states are set before every recorded reset)
     record_reset_chains()
+    record_lh_12rooms()      # (a construction seed of its own: nothing above moves)
 
 
 def face(env, i, target_xy, carrying=None):
@@ -492,6 +493,39 @@ def record_dict_order():
                script=[[N] * 4, [T] + [N] * 3, [T] * 4, [T] * 4, [F] * 4, [T] * 4, [L] * 4, [T] * 4] +
                       np.random.default_rng(7).integers(0, 7, size=(30, 4)).tolist(),
                note=f"8 rooms of even size {rs}: mid-wall doors at (top + bottom) // 2")
+
+
+def record_lh_12rooms():
+    """LockedHallway with 12 rooms of size 4: the geometric door format with doors 8-11, whose unlock bits are the second byte
+    of the mask (include/mgx.h: aux[2]).  Agent 0 stands at door 0 (row 0, left), agents 1 and 2 together at door 9 (row 4, right),
+    each with the door's key; after the scripted unlocks agent 0 is in reach of more doors by the random tail.  A random permutation
+    of the dict's keys every step.  The construction seed is a constant of its own, so the function can run alone
+    (`python oracle/gen_golden.py lh_12rooms`) and no other fixture's seed moves."""
+    from multigrid.core.world_object import Key
+    T, L, F, N = 5, 0, 2, 6
+    colors = ["red", "green", "blue", "purple", "yellow", "grey"]
+    rs = 4
+
+    def door_xy(k):
+        return ((rs - 1) * (1 + k % 2), (k // 2) * (rs - 1) + (rs - 1) // 2)
+
+    def edit(env):
+        for i, k in ((0, 0), (1, 9)):
+            x, y = door_xy(k)
+            assert env.grid.state[x, y, 0] == 4
+            face(env, i, (x, y), carrying=Key(colors[int(env.grid.state[x, y, 1])]))
+        x, y = door_xy(9)
+        env.agents[2].state.pos = env.agents[1].state.pos
+        env.agents[2].state.dir = env.agents[1].state.dir
+        env.agents[2].state.carrying = Key(colors[int(env.grid.state[x, y, 1])])
+    ref_envs.LockedHallwayEnv._default_seed = 0xC0FFEE + 0x1200
+    r = np.random.default_rng(12)
+    orders = np.stack([r.permutation(3) for _ in range(40)]).astype(np.uint8)
+    record("lh_12rooms_rs4_a3_joint", ref_envs.LockedHallwayEnv(num_rooms=12, room_size=rs, agents=3, joint_reward=True),
+           "lockedhallway", 112, None, None, edit=edit,
+           script=[[N] * 3, [T, N, N], [N, T, T], [T] * 3, [F] * 3, [T] * 3, [L] * 3, [T] * 3] +
+                  np.random.default_rng(8).choice([T, T, F, L, 1, N], size=(32, 3)).tolist(),
+           dict_orders=orders, note="12 rooms of size 4: doors 0 and 9 unlocked, the mask crosses its first byte")
 
 
 def record_wrappers():
@@ -1336,4 +1370,7 @@ def spec_of_noreset(env, kind):
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["lh_12rooms"]:
+        record_lh_12rooms()
+    else:
+        main()

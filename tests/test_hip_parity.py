@@ -537,7 +537,10 @@ HOOK_CASES = [
 
 @pytest.mark.parametrize("name,env_id,kw,B,T", HOOK_CASES, ids=[c[0] for c in HOOK_CASES])
 def test_hook_envs_random_rollouts_vs_oracle(name, env_id, kw, B, T):
-    """Section 8f-4 envs: B different generated layouts, random actions, every step vs the oracle; also as one rollout."""
+    """Section 8f-4 envs: B different generated layouts, random actions, every step vs the oracle; also as one rollout.
+    Parity on generated layouts, NOT hook coverage: Playground's kind is `empty` (it has no hook; `events` is not asked of it), and a
+    random walk over the other two reaches their hooks in a handful of env-steps at most.  The hooks are walked densely, through every
+    kernel family, in tests/test_hook_kinds_gpu.py."""
     import multigrid_amd as mg
     from multigrid_amd import envs as E
     spec = mg.spec_for(env_id, **kw)

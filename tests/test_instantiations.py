@@ -12,6 +12,9 @@ files land in the families they were written for.  This one walks the matrix: fo
 and the persistent launch, each against `BatchedMultiGridEnv` on the CPU-oracle backend (tests/util.OracleBackend: the oracle's step
 behind the same host logic) on the same random states -- every output of every step and the state afterwards.  The big batches of the
 streamed cases are compared on slices of the batch (the kernels are data-parallel over envs; the oracle then costs milliseconds).
+The "hook env" of this matrix is BlockedUnlockPickup, the least demanding hook; the other hook kinds (RedBlueDoors, LockedHallway,
+the declared rules) are run-time branches inside the same instantiations and are walked through the same families in
+tests/test_hook_kinds_gpu.py.
 
 tools/kernel_coverage.py records which kernels a run of `pytest -m gpu` launched (profiles/kernels_launched.txt) and
 tests/test_kernel_coverage.py (CPU) fails when the library carries a kernel that is not on that list.

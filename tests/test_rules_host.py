@@ -62,8 +62,9 @@ def test_rules_match_oracle_on_random_states(spec, force_serial):
             assert n_serial > 0, (n_serial, n_total)            # ... and so is the fallback (cell conflicts, presence)
 
 
-COMPACT = [dataclasses.replace(s, cell_bytes=1) for s in (CASES[0], CASES[1], CASES[2], CASES[6], CASES[9])] + [
-    EnvSpec(8, 8, 2, 7, max_steps=40, env_kind="redbluedoors", cell_bytes=1)]
+# (the hook kinds beyond BlockedUnlockPickup -- RedBlueDoors, LockedHallway, rules -- run on compact cells too, on states built for
+# them: tests/test_hook_states.py, test_host_rules_match_the_oracle_on_hook_dense_states; a random state is no state of theirs)
+COMPACT = [dataclasses.replace(s, cell_bytes=1) for s in (CASES[0], CASES[1], CASES[2], CASES[6], CASES[9])]
 
 
 @pytest.mark.parametrize("force_serial", [False, True], ids=["fastpath", "serial"])
@@ -72,8 +73,6 @@ def test_rules_on_compact_cells_match_oracle(spec, force_serial):
     """The same rules on COMPACT one-byte cells (include/mgx.h: MgxCell8, EnvSpec.cell_bytes = 1: type and state coded jointly):
     the host shim packs the tile that way, the rules read / write it through the format-aware accessors, and every output and the
     whole post-step state must equal the oracle's -- which knows nothing about cell formats."""
-    if spec.env_kind == "redbluedoors":
-        pytest.skip("random states of the hook envs come from their own generators (tests/test_hip_parity.py on the GPU)")
     test_rules_match_oracle_on_random_states(spec, force_serial)
 
 
