@@ -173,14 +173,11 @@ __global__ __launch_bounds__(256) void full_obs_kernel(int W, int H, int A, int 
         d[0] = (uint8_t)c; d[1] = (uint8_t)(c >> 8); d[2] = (uint8_t)(c >> 16);
     };
     int i = lane;
-#ifndef MGX_FULL_OBS_BY_OUTPUT
-#define MGX_FULL_OBS_BY_OUTPUT 1
-#endif
     // (round 6) OUTPUT order when the wavefront's slice of the output starts on a dword: a lane owns four consecutive output cells --
     // twelve bytes, three aligned dwords -- and gathers their packed cells from [y][x]: one LDS read per cell and three dword writes
     // per four cells instead of three byte writes per cell, the (e, x, y) decomposition once per four cells (same box: profiles/
     // r6_full_obs.txt).  The ragged last cells and slices that start off a dword keep the input-ordered pass below.
-    if (MGX_FULL_OBS_BY_OUTPUT && (oskew & 3) == 0) {
+    if ((oskew & 3) == 0) {
         const int ngrp = ncell >> 2;
         auto gather4 = [&](const int k, uint32_t (&c)[4]) {
             const int o = 4 * k;

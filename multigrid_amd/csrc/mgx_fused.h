@@ -114,25 +114,6 @@ struct KernelArgs {
     int32_t span_base;  // -DMGX_TIMESTAMPS=1 builds: first record of this launch in g_span (tools/span_probe.py, tools/chain_overlap.py)
 };
 
-#ifndef MGX_EARLY_ARGS
-#define MGX_EARLY_ARGS 2     // 1: the latency family only (DMA instantiations); 2: every instantiation with views <= 7x7 (the C4
-                             // throughput kernel: 18.63-18.83 -> 18.45-18.54 us, three same-box passes; 9x9 and up: the compiler crashes on it)
-#endif
-#ifndef MGX_LATE_ARGS
-#define MGX_LATE_ARGS 1
-#endif
-#ifndef MGX_WRITELANE_NOP
-#define MGX_WRITELANE_NOP 0
-#endif
-#ifndef MGX_LDS_DMA
-#define MGX_LDS_DMA 0
-#endif
-#ifndef MGX_DRAWS_FIRST
-#define MGX_DRAWS_FIRST 0
-#endif
-#ifndef MGX_BUF_STORE
-#define MGX_BUF_STORE 1
-#endif
 // -DMGX_DEBUG_KNOBS=1 (the tools' build, `python -m multigrid_amd.build --debug-knobs` -> lib/libmgx_dbg.so): phase
 // skipping and launch-geometry overrides for profiling.  The product library has neither the exports nor the branches.
 #ifndef MGX_DEBUG_KNOBS
@@ -174,22 +155,11 @@ __device__ __forceinline__ T kernarg_at(size_t offset) {
     typedef const T __attribute__((address_space(4))) *tptr;
     return *(tptr)((cptr)__builtin_amdgcn_kernarg_segment_ptr() + offset);
 }
-#if MGX_LATE_ARGS
 #define MGX_LATE(field) kernarg_at<decltype(KernelArgs::field)>(offsetof(KernelArgs, field))
-#else
-#define MGX_LATE(field) (a.field)
-#endif
 
 // A launch lasts as long as its slowest wavefront, and the slowest is the one that took a rare path (restart, events, sequential
 // fallback): from there on it asks for issue priority over the wavefronts it shares its SIMD with, which finish early anyway.
-#ifndef MGX_RARE_PRIO
-#define MGX_RARE_PRIO 1
-#endif
-#if MGX_RARE_PRIO
 #define MGX_RARE_PATH_PRIO() __builtin_amdgcn_s_setprio(3)
-#else
-#define MGX_RARE_PATH_PRIO() ((void)0)
-#endif
 
 // per-view record written by P1d and read (broadcast) by the wavefront in P2
 // origin: LDS address of the agent's own cell; steps / lo / hi: mgx_rules.h ViewClamp (packed i16 pairs, low half = forward)
@@ -201,50 +171,22 @@ typedef const int8_t __attribute__((address_space(3))) *lds_i8_ptr;
 typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
 typedef const u32_unaligned __attribute__((address_space(3))) *lds_u32_ua_ptr;
 
-#ifndef MGX_SLOTS_SMALL_VIEW
-#define MGX_SLOTS_SMALL_VIEW 64
-#endif
 #ifndef MGX_NO_BIG_PERSIST
 #define MGX_NO_BIG_PERSIST 0
 #endif
 #ifndef MGX_NO_FIXED_SHAPES
 #define MGX_NO_FIXED_SHAPES 0     // 1: build without the shape-specialised instantiations (kShapes below): A/B builds
 #endif
-constexpr int kSlotsSmallView = MGX_SLOTS_SMALL_VIEW;
-// cache policy bits of the obs stores (raw buffer store `aux`: 1 = sc0, 2 = nt, 16 = sc1 on gfx94x/gfx950)
-#ifndef MGX_OBS_AUX
-#define MGX_OBS_AUX 2       // nt: the observation is written once and read by another kernel (C4 -4.6 %, C3 -2 %, C5 -1.7 %)
-#endif
-#ifndef MGX_OBS_AUX_CACHED
-#define MGX_OBS_AUX_CACHED MGX_OBS_AUX   // ... of the instantiations whose grid tensor fits the Infinity Cache (!STREAM)
-#endif
-#ifndef MGX_OH_AUX
-#define MGX_OH_AUX 0        // one-hot observation stores: default policy (nt measured 6 % slower on this 7x larger write stream)
-#endif
-#ifndef MGX_IN_AUX
-#define MGX_IN_AUX 0        // small state loads (agent rows, PCG64 words, step counts, actions) of the STREAM instantiations
-#endif
-#ifndef MGX_OUT_AUX
-#define MGX_OUT_AUX 2       // small per-agent outputs (rows, reward, terminated, dir): nt (round 3: fewer dirty lines for the end-of-kernel
-                            // write-back, C4 19.30 -> 18.82 us over three alternating runs; C2 / C5 unchanged)
-#endif
-// the env lanes' own small stores (PCG64 words, step count, truncated, was_reset): 1 = non-temporal too
-#ifndef MGX_STATE_NT
-#define MGX_STATE_NT 0
-#endif
-#if MGX_STATE_NT
-#define MGX_STORE_SMALL(ptr, val) __builtin_nontemporal_store((val), (ptr))
-#else
-#define MGX_STORE_SMALL(ptr, val) (*(ptr) = (val))
-#endif
-// cache policy bits of the grid tile loads (same encoding)
-#ifndef MGX_TILE_AUX
-#define MGX_TILE_AUX 0
-#endif
-#ifndef MGX_ROUND
-#define MGX_ROUND 16
-#endif
-constexpr int kRound = MGX_ROUND;        // view slots whose obs bytes are staged in LDS at a time (P4/P5)
+constexpr int kSlotsSmallView = 64;
+// Cache policy bits of the kernel's loads and stores (raw buffer `aux`: 0 = default, 1 = sc0, 2 = nt, 16 = sc1 on gfx94x/gfx950).  The
+// env lanes' own small stores (PCG64 words, step count, truncated, was_reset) keep the default policy; the grid tile's loads are nt
+// in the STREAM instantiations only (mgx_fused_body.inc: kTileAux, with its measurement).
+constexpr int kInAux = 0;   // the small state loads of P0: default policy
+constexpr int kObsAux = 2;  // observation stores: nt -- written once and read by another kernel (C4 -4.6 %, C3 -2 %, C5 -1.7 %)
+constexpr int kOhAux = 0;   // one-hot observation stores: default policy (nt measured 6 % slower on this 7x larger write stream)
+constexpr int kSmallOutAux = 2;   // small per-agent outputs (rows, reward, terminated, dir): nt (round 3: fewer dirty lines for the
+                                  // end-of-kernel write-back, C4 19.30 -> 18.82 us over three alternating runs; C2 / C5 unchanged)
+constexpr int kRound = 16;               // view slots whose obs bytes are staged in LDS at a time (P4/P5)
 
 // View slots per wavefront.  Views of up to 7x7 (one lane pass per view): 64 slots in the throughput instantiations, whose
 // cell registers hold two slots each (the per-agent phases then run on all 64 lanes: their cost per view halves); 32 in the
@@ -344,7 +286,7 @@ inline int grid_cell_bytes_of(const MgxSpec &sp) { return sp.cell_bytes == 3 ? 3
 
 // WHAT is launched, as a value: the kernel family (the MODE template parameter of mgx_fused_kernel) and the two options that select
 // an instantiation.  Every launch decision of the host is a function of (spec, batch, form): the specs a form serves and its geometry
-// (mgx_kernels.hip: check_spec, plan_launch), a wavefront's view slots and LDS carve (below), the instantiation (launch_view).
+// (mgx_kernels.hip: check_spec, plan_launch), a wavefront's view slots and LDS carve (below), the instantiation (choose_view).
 struct LaunchForm {
     enum Family : int { kGenObs = 0, kStep = 1, kRollout = 2, kPersistent = 3 };
     enum : int { kOneHot = 4, kGenerate = 8 };             // (bits of mode())
@@ -361,7 +303,7 @@ struct LaunchForm {
     constexpr bool narrow() const { return roll() || obs_only(); }                         // (slots_per_wave: `narrow`)
     // the plain step: the only form with shape-specialised, runtime-compiled and small-group instantiations (kShapes, has_small_groups)
     constexpr bool plain_step() const { return family == kStep && !one_hot && !generate; }
-    constexpr int mode() const { return family | (one_hot ? kOneHot : 0) | (generate ? kGenerate : 0); }   // what launch_view switches on
+    constexpr int mode() const { return family | (one_hot ? kOneHot : 0) | (generate ? kGenerate : 0); }   // what choose_view switches on
 };
 
 constexpr int kGroupSlots = 16;           // (== kGroup, defined with the gather below)
@@ -378,10 +320,7 @@ inline int wave_lds_bytes(const MgxSpec &sp, int Gw, LaunchForm form, int grp) {
 }
 
 constexpr int kLdsPerCU = 160 * 1024;
-#ifndef MGX_LDS_WAVE_BUDGET
-#define MGX_LDS_WAVE_BUDGET (12 * 1024)
-#endif
-constexpr int kLdsWaveBudget = MGX_LDS_WAVE_BUDGET;     // keeps >= 12 wavefronts per CU resident
+constexpr int kLdsWaveBudget = 12 * 1024;     // keeps >= 12 wavefronts per CU resident
 
 // Envs per wavefront: as many as fit the wave's view slots and its LDS budget; fewer when the batch is too small
 // to give every SIMD of the chip a few wavefronts (then latency, not throughput, is what matters).
@@ -416,7 +355,7 @@ inline int choose_group(const MgxSpec &sp, int64_t batch) {
 // runs beside four waves' VALU work) and has none.  The table holds the shapes BASELINE.json names, at the envs-per-wavefront
 // choose_Gw gives them in the latency regime; every other shape, and these at other launch geometries, run the generic kernels.
 struct FixedShape { int W, H, A, Gw; bool hooks; int V; bool dma, stream; int cb = kCellBytes; int ns = 0; int pitch = 0; };   // (dma / stream: the
-                                                  // instantiation family, launch_mode; cb: bytes per grid cell; ns > 0: a RESIDENT shape of the
+                                                  // instantiation family, choose_kernel; cb: bytes per grid cell; ns > 0: a RESIDENT shape of the
                                                   // rollout / persistent kernels -- 64 view slots, ns slices per wavefront, LdsCarve)
 constexpr FixedShape kShapes[] = {
     {0, 0, 0, 0, false, 0, false, false},
@@ -442,7 +381,7 @@ constexpr FixedShape kShapes[] = {
     // the registers from asking for the occupancy (amdgpu_waves_per_eu(4): the compiler rematerialises instead of holding)
     {16, 16, 4, 16, false, 7, false, false, kCellBytes, 1, 15},
 #ifdef MGX_JIT_SHAPE
-    {MGX_JIT_SHAPE},                            // 5: ANY other shape, compiled at run time (hipRTC) from these same headers with its
+    {MGX_JIT_SHAPE},                            // kNumShapes - 1: ANY other shape, compiled at run time (hipRTC) from these same headers with its
                                                 //    launch geometry as MGX_JIT_SHAPE (multigrid_amd/jit.py, mgx_shape_register)
 #endif
 };
@@ -505,22 +444,11 @@ __device__ __forceinline__ int mad24(int a, int b, int c) {
 }
 
 // lane `s` of `old` := the wave-uniform value `sval` (v_writelane_b32; clang has no builtin for it)
-#ifndef MGX_ASM_WRITELANE
-#define MGX_ASM_WRITELANE 1
-#endif
 __device__ __forceinline__ uint32_t set_lane(uint32_t old, uint32_t sval, const int s) {
-#if MGX_ASM_WRITELANE
     // (the data operand of v_writelane has no software hazard: only an SGPR used as LANE SELECT after a VALU write needs
-    // wait states; the lane is an immediate here.  -DMGX_WRITELANE_NOP=1 restores the conservative s_nop of round 1.)
-#if MGX_WRITELANE_NOP
-    asm("s_nop 1\n\tv_writelane_b32 %0, %1, %2" : "+v"(old) : "s"(sval), "n"(s));
-#else
+    // wait states; the lane is an immediate here)
     asm("v_writelane_b32 %0, %1, %2" : "+v"(old) : "s"(sval), "n"(s));
-#endif
     return old;
-#else
-    return __builtin_amdgcn_inverse_ballot_w64(1ull << s) ? sval : old;
-#endif
 }
 
 // Raw buffer resource over `bytes` bytes at `base` (wave-uniform).  Lanes whose offset falls outside read zeros and
@@ -547,11 +475,7 @@ __device__ __forceinline__ uint64_t state_is_open(uint32_t c) {
 // address carries the view's offset; the see-behind ballot of a shared pass is split by fixed lane ranges on the scalar unit
 // (one v_writelane per view, as before), and P4 joins three views' 17-bit visibility words into the pass's lane predicate.
 // Only 9x9 views have a remainder small enough (3 R <= 64); every other view size keeps one view per pass.
-#ifndef MGX_PACK3
-#define MGX_PACK3 1
-#endif
-template <int V> constexpr bool kPack3 = (MGX_PACK3 != 0) && (V * V > 64) && (V * V <= 128)
-                                         && 3 * (V * V - 64) <= 64;
+template <int V> constexpr bool kPack3 = (V * V > 64) && (V * V <= 128) && 3 * (V * V - 64) <= 64;
 constexpr int pack3_passes(int n) { return (n + 2) / 3; }      // remainder passes of a block of n view slots
 
 template <int V, int NIT>
@@ -778,10 +702,7 @@ __device__ __forceinline__ void gather_group_pk3(const KernelArgs &a, const int 
     (void)sbHi;
 }
 
-#ifndef MGX_GROUP
-#define MGX_GROUP 16
-#endif
-constexpr int kGroup = MGX_GROUP;      // slots gathered (P2) / written (P4) as one straight-line block
+constexpr int kGroup = 16;             // slots gathered (P2) / written (P4) as one straight-line block
 
 // ---- P2 / P4 of the one-step kernels for views of one lane pass on 16-bit cells: one lane per view LINE (mgx_rules.h, "line map").
 // Pass p of the wavefront, lane l: view slot 8 p + (l >> 3), line j = l & 7 (the lanes with j >= V idle: 56 of 64 busy at 7x7, where
@@ -868,7 +789,7 @@ __device__ __forceinline__ void gather_all(const KernelArgs &a, const int wave, 
 // C8: the grid is held as COMPACT one-byte cells (include/mgx.h: MgxCell8; MgxSpec.cell_bytes = 1): one-step and gen_obs kernels of
 // the throughput / streamed families only.
 // B3: the grid tensors are the reference's byte triples u8[B,H,W,3] (MgxSpec.cell_bytes = 3), packed into the 16-bit tile by P0.
-template <int V, int MODE, bool HOOKS, bool AR, bool OH = false, bool GEN = false, bool STREAM = false, bool DMA = (MGX_LDS_DMA != 0),
+template <int V, int MODE, bool HOOKS, bool AR, bool OH = false, bool GEN = false, bool STREAM = false, bool DMA = false,
           int GRP = kGroup, int SHAPE = 0, bool C8 = false, bool B3 = false>
 __global__ __launch_bounds__(kMaxThreads) void mgx_fused_kernel(const KernelArgs a) {
 #include "mgx_fused_body.inc"
@@ -879,8 +800,10 @@ __global__ __launch_bounds__(kMaxThreads) void mgx_fused_kernel(const KernelArgs
 template <int MODE, bool AR>
 __global__ __launch_bounds__(kMaxThreads) __attribute__((amdgpu_waves_per_eu(4)))
 void mgx_resident_kernel(const KernelArgs a) {
-    constexpr int V = 7, GRP = kGroup, SHAPE = kShapeResident4;
-    constexpr bool HOOKS = false, OH = false, GEN = false, STREAM = false, DMA = false, C8 = false, B3 = false;
+    constexpr int V = 7;
+    constexpr bool HOOKS = false, OH = false, GEN = false, STREAM = false, DMA = false;
+    constexpr int GRP = kGroup, SHAPE = kShapeResident4;
+    constexpr bool C8 = false, B3 = false;
 #include "mgx_fused_body.inc"
 }
 
@@ -891,13 +814,12 @@ void mgx_resident_kernel(const KernelArgs a) {
 template <int V, bool OH, bool STREAM, bool DMA, bool C8 = false, bool B3 = false>
 __global__ __launch_bounds__(kMaxThreads) __attribute__((amdgpu_waves_per_eu(6)))
 void mgx_obs_kernel(const KernelArgs a) {
-    constexpr int MODE = 0, GRP = kGroup, SHAPE = 0;
+    constexpr int MODE = 0;
     constexpr bool HOOKS = false, AR = false, GEN = false;
+    constexpr int GRP = kGroup, SHAPE = 0;
 #include "mgx_fused_body.inc"
 }
 
-// The kernel instantiation for (V, mode, hooks, auto-reset) and its launch.  `hip_err` receives the HIP error code of a
-// failed launch (mgx_last_hip_error).
 // The small-group latency instantiations (GRP 4 / 8: a wavefront owns ONE group of 4 or 8 view slots) exist only in the tools'
 // build (-DMGX_DEBUG_KNOBS=1, lib/libmgx_dbg.so; mgx_debug_set_group), for the step kernel of views up to 9x9.  Measured
 // (tools/group_sweep.py, profiles/r3_small_group_sweep.txt): they do NOT pay -- every additional wavefront on a SIMD costs its
@@ -940,211 +862,240 @@ inline int match_resident_shape(const KernelArgs &ka, bool hooks) {
     return 0;
 }
 
-#if !defined(__HIPCC_RTC__)      // host side: the launchers (a runtime-compiled translation unit holds kernels only)
+#if !defined(__HIPCC_RTC__)      // host side: choosing an instantiation and launching it (a runtime-compiled translation unit holds kernels only)
 // Shape-specialised kernels compiled at run time and handed to mgx_shape_register (mgx_kernels.hip): looked up by the launch geometry
 // the host derived, exactly like the built-in kShapes entries.  fn[ar]: the plain step without / with the fused auto-reset.
 struct JitShape { FixedShape f; int vpw, wave_lds; hipFunction_t fn[2]; };
 const JitShape *jit_shape_lookup(const KernelArgs &ka, bool hooks);
-// The tail of every launcher below: `kern` with the plan's geometry -- or, `occupancy`: query only (mgx_sub_shards, the persistent
-// launch's residency check), the workgroups of this instantiation that one CU holds at a time.
-inline int launch_kernel(void (*kern)(const KernelArgs), const KernelArgs &ka, int threads, int lds_bytes, int64_t nwg, hipStream_t stream,
+
+// ---- WHICH instantiation.  A VARIANT names the compile-time parameters of the kernels field by field (a field it does not mention has
+// Variant's default); HOOKS and AR, the two a launch decides at run time, are not among them: kernel_of below picks those.
+typedef void (*KernelFn)(const KernelArgs);
+struct Variant {
+    static constexpr int mode = LaunchForm::kStep, grp = kGroup, shape = 0;
+    static constexpr bool oh = false, gen = false, stream = false, dma = false, c8 = false, b3 = false;
+};
+// (a launch form's kernels, then the families of a form: each changes the fields it is about)
+template <int MODE, bool OH, bool GEN> struct FormOf : Variant { static constexpr int mode = MODE; static constexpr bool oh = OH, gen = GEN; };
+template <class K> struct Streamed : K { static constexpr bool stream = true; };
+template <class K, int GRP = kGroup> struct Latency : K { static constexpr bool dma = true; static constexpr int grp = GRP; };
+template <class K> struct Compact : K { static constexpr bool c8 = true; };
+template <class K> struct ByteGrid : K { static constexpr bool b3 = true; };
+// ... and entry S of kShapes in family K: what the table says about the shape is taken from the table
+template <class K, int S> struct Shaped : K {
+    static constexpr int shape = S;
+    static constexpr bool stream = kShapes[S].stream, c8 = kShapes[S].cb == 1;
+    // (the persistent form of a latency shape is not DMA: MODE 3 has the rollout's carve and no DMA / STREAM families)
+    static constexpr bool dma = kShapes[S].dma && K::mode != LaunchForm::kPersistent;
+};
+
+// The (HOOKS, AR) pairs a variant is instantiated for, as the values each of the two may take: nothing outside them is ever named, so
+// nothing outside them is compiled.
+enum : unsigned { kNever = 1, kAlways = 2, kEither = kNever | kAlways };
+template <class K> constexpr unsigned hooks_of() {
+    if (K::shape != 0) return kShapes[K::shape].hooks ? kAlways : kNever;       // (a shape entry is one env kind's)
+    if (K::mode == LaunchForm::kGenObs) return kNever;                          // (gen_obs never runs a hook)
+    // compact cells, one-hot output (round 6): the hook-free step (big grids are Empty-style arenas; the hook envs are small and keep the
+    // 16-bit cells); ... and the hook-free rollout / persistent kernels (32 view slots, the tile resident as bytes)
+    if (K::c8 && (K::oh || K::mode > LaunchForm::kStep)) return kNever;
+    return kEither;
+}
+template <class K> constexpr unsigned ar_of() {
+    return (K::mode == LaunchForm::kGenObs || K::gen) ? kNever : kEither;       // (generation replaces the pool pick-up)
+}
+
+// The ONE place that spells the kernels' template parameter lists.
+template <int V, class K, bool HOOKS, bool AR>
+constexpr KernelFn entry_point() {
+    if constexpr (K::shape == kShapeResident4)
+        return mgx_resident_kernel<K::mode, AR>;
+    // (the byte-grid gen_obs holds its conversion's staging registers: it takes the step kernels' entry point, without the
+    // occupancy request of mgx_obs_kernel that would make it spill)
+    else if constexpr (K::mode == LaunchForm::kGenObs && V <= 7 && !K::b3)
+        return mgx_obs_kernel<V, K::oh, K::stream, K::dma, K::c8, K::b3>;
+    else
+        return mgx_fused_kernel<V, K::mode, HOOKS, AR, K::oh, K::gen, K::stream, K::dma, K::grp, K::shape, K::c8, K::b3>;
+}
+// ... and the one run-time choice among a variant's pairs (nullptr: the variant has no such pair)
+template <int V, class K, bool HOOKS>
+inline KernelFn kernel_with(bool ar) {
+    if constexpr ((ar_of<K>() & kAlways) != 0) { if (ar) return entry_point<V, K, HOOKS, true>(); }
+    if constexpr ((ar_of<K>() & kNever) != 0) { if (!ar) return entry_point<V, K, HOOKS, false>(); }
+    return nullptr;
+}
+template <int V, class K>
+inline KernelFn kernel_of(bool hooks, bool ar) {
+    if constexpr ((hooks_of<K>() & kAlways) != 0) { if (hooks) return kernel_with<V, K, true>(ar); }
+    if constexpr ((hooks_of<K>() & kNever) != 0) { if (!hooks) return kernel_with<V, K, false>(ar); }
+    return nullptr;
+}
+
+// Whether family F at view size V has an instantiation for entry k of kShapes.
+constexpr int kShapeGenerated = 3;       // BlockedUnlockPickup x 2 (C3 with its episodes generated on the device): the one shape whose
+                                         // generated step has an instantiation, in the latency family
+static_assert(kShapes[kShapeGenerated].hooks && kShapes[kShapeGenerated].dma && kShapes[kShapeGenerated].V == 7 && kShapes[kShapeGenerated].A == 2,
+              "kShapeGenerated must name the BlockedUnlockPickup entry of kShapes");
+template <int V, class F>
+constexpr bool shape_serves(int k) {
+    const FixedShape &f = kShapes[k];
+    if (MGX_NO_FIXED_SHAPES || F::oh || F::b3 || F::grp != kGroup || f.V != V || (f.cb == 1) != F::c8) return false;
+    // the resident forms of the C4 shape (64 view slots, one or two slices of 16 envs per wavefront): rollout and persistent kernels.
+    // (kShapeResident4: rollouts only.  A persistent launch of 4 x 128 VGPRs per SIMD would leave the producer / consumer kernels of its
+    // own hand-shake no register to run in -- resident_shape() keeps that launch on shapes 7 / 8)
+    if (f.ns > 0) return F::mode == LaunchForm::kRollout || (F::mode == LaunchForm::kPersistent && k != kShapeResident4);
+    // the persistent step kernel at the latency shapes (C2 / C4's 8-GPU and 4-GPU shares, C3)
+    if (F::mode == LaunchForm::kPersistent) return f.dma;
+    if (F::gen) return F::dma && k == kShapeGenerated;
+    // the plain step, picked only when the launch geometry the host derived is exactly the one the instantiation was compiled for:
+    // the entry's dma / stream are this family's (plan_launch set the flags)
+    return F::mode == LaunchForm::kStep && f.dma == F::dma && f.stream == F::stream;
+}
+template <int V, class F>
+constexpr bool serves_shapes(bool resident) {
+    for (int k = 1; k < kNumShapes; ++k)
+        if (shape_serves<V, F>(k) && (kShapes[k].ns > 0) == resident) return true;
+    return false;
+}
+// The kernel of the entry that matched (match_fixed_shape / match_resident_shape), or nullptr: a walk over the entries F can match.
+template <int V, class F, int K = 1>
+inline KernelFn shape_kernel(int matched, bool ar) {
+    if constexpr (K < kNumShapes) {
+        if constexpr (shape_serves<V, F>(K)) { if (matched == K) return kernel_of<kShapes[K].V, Shaped<F, K>>(kShapes[K].hooks, ar); }
+        return shape_kernel<V, F, K + 1>(matched, ar);
+    } else {
+        return nullptr;
+    }
+}
+
+// What a launch runs: a kernel of this library, or a runtime-compiled one -- or the code it is refused with.
+struct KernelChoice { int rc; KernelFn kern; hipFunction_t jit; };
+inline KernelChoice refused(int rc) { return {rc, nullptr, nullptr}; }
+
+// Within family F: the geometry the family's kernels are compiled for, then the shape entry, the runtime-compiled shape, and last the
+// generic kernel.  `jit_ok`: a real launch (an occupancy query is about this library's kernels).
+template <int V, class F>
+inline KernelChoice choose_in_family(const KernelArgs &ka, bool jit_ok) {
+    constexpr bool kCells16 = !F::c8 && !F::b3;
+    if (ka.grp != F::grp) return refused(MGX_ERR_INVALID_ARGUMENT);       // (the host-side carve was made for another group size)
+    if constexpr (!kCells16) {
+        // (compact cells and byte grids have no latency family; C8: 32 view slots: one decoded cell per register)
+        if ((F::mode < LaunchForm::kRollout && (ka.flags & 2)) || (F::c8 && ka.vpw > 32)) return refused(MGX_ERR_INVALID_ARGUMENT);
+    }
+    const bool hooks = F::mode != LaunchForm::kGenObs && ka.sp.env_kind != MGX_KIND_EMPTY;
+    // A non-null ka.pool_grid is what selects the instantiations WITH the fused auto-reset
+    const bool ar = ar_of<F>() == kEither && ka.pool_grid != nullptr;
+    if constexpr (hooks_of<F>() == kNever) { if (hooks) return refused(MGX_ERR_UNSUPPORTED); }
+    if constexpr (kCells16) {
+        if (ka.ns > 0) {                    // a resident geometry: its instantiation, or plan_launch chose one no instantiation has
+            KernelFn kern = nullptr;
+            if constexpr (serves_shapes<V, F>(true)) kern = shape_kernel<V, F>(match_resident_shape(ka, hooks), ar);
+            return kern ? KernelChoice{MGX_OK, kern, nullptr} : refused(MGX_ERR_INVALID_ARGUMENT);
+        }
+    }
+    if constexpr (serves_shapes<V, F>(false)) {
+        if (KernelFn kern = shape_kernel<V, F>(match_fixed_shape(ka, hooks, F::mode == LaunchForm::kPersistent), ar))
+            return {MGX_OK, kern, nullptr};
+    }
+    if constexpr (LaunchForm{(LaunchForm::Family)F::mode, F::oh, F::gen}.plain_step() && kCells16 && F::grp == kGroup && !MGX_NO_FIXED_SHAPES) {
+        if (jit_ok) {
+            if (const JitShape *js = jit_shape_lookup(ka, hooks))           // a runtime-compiled instantiation of this very geometry
+                return {MGX_OK, nullptr, js->fn[ar ? 1 : 0]};
+        }
+    }
+    return {MGX_OK, kernel_of<V, F>(hooks, ar), nullptr};
+}
+
+// The family, from the grid's cell format and the plan's flags (ka.flags bit 0: streamed, bit 1: latency).
+template <int V, int MODE, bool OH, bool GEN>
+inline KernelChoice choose_kernel(const KernelArgs &ka, bool jit_ok) {
+    using Form = FormOf<MODE, OH, GEN>;
+    using LF = LaunchForm;
+    const bool streamed = (ka.flags & 1) != 0, latency = (ka.flags & 2) != 0;
+    // Compact cells (C8): the plain step / gen_obs of the throughput and streamed families -- hooks and auto-reset included --, the
+    // hook-free step with one-hot output and the hook-free rollout / persistent kernels; no generation or latency (LDS-DMA)
+    // instantiation: plan_launch never asks for one on such a spec.
+    if (ka.sp.cell_bytes == 1) {
+        if constexpr (GEN || (OH && MODE != LF::kStep)) return refused(MGX_ERR_UNSUPPORTED);
+        else if constexpr (MODE >= LF::kRollout) return choose_in_family<V, Compact<Form>>(ka, jit_ok);     // (rollouts read the tile once per launch)
+        else return streamed ? choose_in_family<V, Streamed<Compact<Form>>>(ka, jit_ok) : choose_in_family<V, Compact<Form>>(ka, jit_ok);
+    }
+    // Byte grids (B3, MgxSpec.cell_bytes = 3): the plain step / gen_obs only.  (No streamed family: a u8[B,H,W,3] tensor beyond the
+    // Infinity Cache is loaded with the default policy -- 35 instantiations nobody asked for, round 6)
+    if (ka.sp.cell_bytes == 3) {
+        if constexpr (GEN || OH || MODE >= LF::kRollout) return refused(MGX_ERR_UNSUPPORTED);
+        else return choose_in_family<V, ByteGrid<Form>>(ka, jit_ok);
+    }
+    if constexpr (MODE < LF::kRollout && !GEN) {            // (rollouts read the tile once per launch; GEN: small envs)
+        if (streamed) return choose_in_family<V, Streamed<Form>>(ka, jit_ok);
+        if constexpr (!OH) {
+            if (latency) {
+                if constexpr (has_small_groups(V, MODE, OH, GEN)) {
+                    if (ka.grp == 4) return choose_in_family<V, Latency<Form, 4>>(ka, jit_ok);
+                    if (ka.grp == 8) return choose_in_family<V, Latency<Form, 8>>(ka, jit_ok);
+                }
+                return choose_in_family<V, Latency<Form>>(ka, jit_ok);
+            }
+        }
+    }
+    // GEN (round 3): the plain generated step at 7x7 views also has its latency instantiation (LDS-DMA tile, one cell per register)
+    if constexpr (GEN && MODE == LF::kStep && !OH && V == 7) {
+        if (latency) return choose_in_family<V, Latency<Form>>(ka, jit_ok);
+    }
+    return choose_in_family<V, Form>(ka, jit_ok);
+}
+
+template <int V>
+inline KernelChoice choose_view(LaunchForm form, const KernelArgs &ka, bool jit_ok) {
+    using F = LaunchForm;
+    switch (form.mode()) {
+    case F::gen_obs().mode(): return choose_kernel<V, F::kGenObs, false, false>(ka, jit_ok);
+    case F::step().mode(): return choose_kernel<V, F::kStep, false, false>(ka, jit_ok);
+    case F::rollout().mode(): return choose_kernel<V, F::kRollout, false, false>(ka, jit_ok);
+    case F::persistent().mode():
+        // (hipcc 7.2 crashes at -O3 on the persistent kernels of the three largest views with the bounds checks / the debug knobs
+        // compiled in.  The checked and the tools' builds compile those units at -O2 (multigrid_amd/build.py: flags) and carry
+        // them; only the single-translation-unit timestamps build, which wants -O3 code for its stamps, leaves them out.)
+        if constexpr (MGX_NO_BIG_PERSIST != 0 && V >= 11) return refused(MGX_ERR_UNSUPPORTED);
+        else return choose_kernel<V, F::kPersistent, false, false>(ka, jit_ok);
+    case F::gen_obs().with_one_hot().mode(): return choose_kernel<V, F::kGenObs, true, false>(ka, jit_ok);
+    case F::step().with_one_hot().mode(): return choose_kernel<V, F::kStep, true, false>(ka, jit_ok);
+    case F::rollout().with_one_hot().mode(): return choose_kernel<V, F::kRollout, true, false>(ka, jit_ok);
+    case F::step().with_generate().mode(): return choose_kernel<V, F::kStep, false, true>(ka, jit_ok);
+    case F::step().with_one_hot().with_generate().mode(): return choose_kernel<V, F::kStep, true, true>(ka, jit_ok);
+    default: return refused(MGX_ERR_INVALID_ARGUMENT);      // (no such instantiation: generation is the one-step kernels' tail)
+    }
+}
+
+// ---- ... and its launch with the plan's geometry -- or, `occupancy`: query only (mgx_sub_shards, the persistent launch's residency
+// check), the workgroups of the chosen instantiation that one CU holds at a time.  `hip_err` receives the HIP error code of a failed
+// launch (mgx_last_hip_error).
+inline int launch_choice(const KernelChoice &c, const KernelArgs &ka, int threads, int lds_bytes, int64_t nwg, hipStream_t stream,
                          int *hip_err, int *occupancy) {
+    if (c.rc != MGX_OK) return c.rc;
     hipError_t e = hipSuccess;
-    if (lds_bytes > 64 * 1024) e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+    if (c.jit) {
+        size_t arg_size = sizeof(KernelArgs);
+        void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, const_cast<KernelArgs *>(&ka), HIP_LAUNCH_PARAM_BUFFER_SIZE, &arg_size,
+                          HIP_LAUNCH_PARAM_END};
+        e = hipModuleLaunchKernel(c.jit, (unsigned)nwg, 1, 1, (unsigned)threads, 1, 1, (unsigned)lds_bytes, stream, nullptr, config);
+        if (e != hipSuccess) { *hip_err = (int)e; (void)hipGetLastError(); return MGX_ERR_LAUNCH; }
+        return MGX_OK;
+    }
+    if (lds_bytes > 64 * 1024) e = hipFuncSetAttribute(reinterpret_cast<const void *>(c.kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
     if (e == hipSuccess && occupancy)
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(occupancy, reinterpret_cast<const void *>(kern), threads, (size_t)lds_bytes);
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(occupancy, reinterpret_cast<const void *>(c.kern), threads, (size_t)lds_bytes);
     if (e != hipSuccess) { *hip_err = (int)e; (void)hipGetLastError(); return MGX_ERR_LAUNCH; }   // (off HIP's sticky state too)
     if (occupancy) return MGX_OK;
-    hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(threads), (size_t)lds_bytes, stream, ka);
+    hipLaunchKernelGGL(c.kern, dim3((unsigned)nwg), dim3(threads), (size_t)lds_bytes, stream, ka);
     e = hipGetLastError();
     if (e != hipSuccess) { *hip_err = (int)e; return MGX_ERR_LAUNCH; }
     return MGX_OK;
 }
 
-// Compact cells (C8): the plain step / gen_obs of the throughput and streamed families -- hooks and auto-reset included, no one-hot,
-// generation, rollout or latency (LDS-DMA) instantiation: plan_launch never asks for one on such a spec.
-// (... and, with C8 = false / B3 = true, the byte-grid family: the same set of kernels for MgxSpec.cell_bytes = 3)
-template <int V, int MODE, bool STREAM, bool C8 = true, bool OH = false>
-inline int launch_compact(const KernelArgs &ka, int threads, int lds_bytes, int64_t nwg, hipStream_t stream, int *hip_err, int *occupancy) {
-    constexpr bool B3 = !C8;
-    if constexpr (MODE > 1 && C8 && !OH && !STREAM) {
-        // compact cells, round 6: the hook-free rollout / persistent kernels (32 view slots, the tile resident as bytes)
-        if (ka.grp != kGroup || ka.vpw > 32) return MGX_ERR_INVALID_ARGUMENT;
-        if (ka.sp.env_kind != MGX_KIND_EMPTY) return MGX_ERR_UNSUPPORTED;
-        const bool ar = ka.pool_grid != nullptr;
-        void (*kern)(const KernelArgs) = ar ? mgx_fused_kernel<V, MODE, false, true, false, false, false, false, kGroup, 0, true, false>
-                                            : mgx_fused_kernel<V, MODE, false, false, false, false, false, false, kGroup, 0, true, false>;
-        return launch_kernel(kern, ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
-    } else if constexpr (MODE > 1 || (OH && (MODE != 1 || !C8))) {
-        return MGX_ERR_UNSUPPORTED;
-    } else {
-        if constexpr (!STREAM && C8) {    // (byte grids have no streamed family: a u8[B,H,W,3] tensor beyond the Infinity Cache is
-                                          // loaded with the default policy -- 35 instantiations nobody asked for, round 6)
-            if (ka.flags & 1) return launch_compact<V, MODE, true, C8, OH>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
-        }
-        if (ka.grp != kGroup || (ka.flags & 2) || (C8 && ka.vpw > 32)) return MGX_ERR_INVALID_ARGUMENT;     // (C8: 32 view slots: one decoded cell per register)
-        void (*kern)(const KernelArgs) = nullptr;
-        const bool hooks = MODE != 0 && ka.sp.env_kind != MGX_KIND_EMPTY;
-        const bool ar = MODE != 0 && ka.pool_grid != nullptr;
-        constexpr bool S = MODE != 0;
-        if constexpr (C8 && !OH && MODE == 1 && V == 9 && STREAM && !MGX_NO_FIXED_SHAPES) {
-            if (match_fixed_shape(ka, hooks) == 5)
-                kern = ar ? mgx_fused_kernel<V, 1, false, true, false, false, true, false, kGroup, 5, true>
-                          : mgx_fused_kernel<V, 1, false, false, false, false, true, false, kGroup, 5, true>;
-        }
-        if constexpr (C8 && !OH && MODE == 1 && V == 9 && !STREAM && !MGX_NO_FIXED_SHAPES) {
-            if (match_fixed_shape(ka, hooks) == 6)
-                kern = ar ? mgx_fused_kernel<V, 1, false, true, false, false, false, false, kGroup, 6, true>
-                          : mgx_fused_kernel<V, 1, false, false, false, false, false, false, kGroup, 6, true>;
-        }
-        if constexpr (OH) {
-            // compact cells, one-hot output (round 6): the hook-free step (big grids are Empty-style arenas; the hook envs are small
-            // and keep the 16-bit cells)
-            if (hooks) return MGX_ERR_UNSUPPORTED;
-            kern = ar ? mgx_fused_kernel<V, 1, false, true, true, false, STREAM, false, kGroup, 0, true, false>
-                      : mgx_fused_kernel<V, 1, false, false, true, false, STREAM, false, kGroup, 0, true, false>;
-        }
-        if (!kern) {
-            // (the byte-grid gen_obs holds its conversion's staging registers: it takes the step kernels' entry point, without the
-            // occupancy request of mgx_obs_kernel that would make it spill)
-            if constexpr (MODE == 0 && V <= 7 && !B3)
-                kern = mgx_obs_kernel<V, false, STREAM, false, C8, B3>;
-            else
-                kern = hooks ? (ar ? mgx_fused_kernel<V, MODE, S, S, false, false, STREAM, false, kGroup, 0, C8, B3>
-                                   : mgx_fused_kernel<V, MODE, S, false, false, false, STREAM, false, kGroup, 0, C8, B3>)
-                             : (ar ? mgx_fused_kernel<V, MODE, false, S, false, false, STREAM, false, kGroup, 0, C8, B3>
-                                   : mgx_fused_kernel<V, MODE, false, false, false, false, STREAM, false, kGroup, 0, C8, B3>);
-        }
-        return launch_kernel(kern, ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
-    }
-}
-
-template <int V, int MODE, bool OH, bool GEN = false, bool STREAM = false, bool DMA = false, int GRP = kGroup>
-inline int launch_mode(const KernelArgs &ka, int threads, int lds_bytes, int64_t nwg, hipStream_t stream, int *hip_err, int *occupancy) {
-    if (ka.sp.cell_bytes == 1 || ka.sp.cell_bytes == 3) {  // compact cells / byte grids: their own, smaller families
-        if constexpr (!OH && !GEN && !STREAM && !DMA && GRP == kGroup) {
-            if (ka.sp.cell_bytes == 1) return launch_compact<V, MODE, false, true>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
-            return launch_compact<V, MODE, false, false>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
-        } else if constexpr (OH && MODE == 1 && !GEN && !STREAM && !DMA && GRP == kGroup) {
-            if (ka.sp.cell_bytes == 1) return launch_compact<V, MODE, false, true, true>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
-            return MGX_ERR_UNSUPPORTED;
-        } else return MGX_ERR_UNSUPPORTED;
-    }
-    if constexpr (!STREAM && !DMA && MODE < 2 && !GEN) {    // (rollouts read the tile once per launch; GEN: small envs)
-        if (ka.flags & 1) return launch_mode<V, MODE, OH, GEN, true, false>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
-        if constexpr (!OH) {
-            if (ka.flags & 2) {
-                if constexpr (has_small_groups(V, MODE, OH, GEN)) {
-                    if (ka.grp == 4) return launch_mode<V, MODE, OH, GEN, false, true, 4>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
-                    if (ka.grp == 8) return launch_mode<V, MODE, OH, GEN, false, true, 8>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
-                }
-                return launch_mode<V, MODE, OH, GEN, false, true>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
-            }
-        }
-    }
-    // GEN (round 3): the plain generated step at 7x7 views also has its latency instantiation (LDS-DMA tile, one cell per register)
-    if constexpr (GEN && !DMA && !STREAM && MODE == 1 && !OH && V == 7 && GRP == kGroup) {
-        if (ka.flags & 2) return launch_mode<V, MODE, OH, true, false, true>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
-    }
-    if (ka.grp != GRP) return MGX_ERR_INVALID_ARGUMENT;       // (the host-side carve was made for another group size)
-    void (*kern)(const KernelArgs) = nullptr;
-    const bool hooks = MODE != 0 && ka.sp.env_kind != MGX_KIND_EMPTY;        // (gen_obs never runs a hook)
-    const bool ar = MODE != 0 && ka.pool_grid != nullptr;
-    constexpr bool S = MODE != 0;
-    // the shape-specialised instantiations (kShapes): the plain step of the latency family at 7x7 views, picked only when the
-    // launch geometry the host derived is exactly the one the instantiation was compiled for
-    if constexpr (MODE == 1 && !OH && !GEN && GRP == kGroup && !MGX_NO_FIXED_SHAPES) {
-        const int shape = match_fixed_shape(ka, hooks);          // (its V / dma / stream are this instantiation's: plan_launch set the flags)
-        if constexpr (V == 7 && DMA && !STREAM) {
-            switch (shape) {
-            case 1: kern = ar ? mgx_fused_kernel<V, 1, false, true, false, false, false, true, kGroup, 1> : mgx_fused_kernel<V, 1, false, false, false, false, false, true, kGroup, 1>; break;
-            case 2: kern = ar ? mgx_fused_kernel<V, 1, false, true, false, false, false, true, kGroup, 2> : mgx_fused_kernel<V, 1, false, false, false, false, false, true, kGroup, 2>; break;
-            case 3: kern = ar ? mgx_fused_kernel<V, 1, true, true, false, false, false, true, kGroup, 3> : mgx_fused_kernel<V, 1, true, false, false, false, false, true, kGroup, 3>; break;
-            default: break;
-            }
-        }
-        if constexpr (V == 9 && !DMA && STREAM) {
-            if (shape == 4) kern = ar ? mgx_fused_kernel<V, 1, false, true, false, false, true, false, kGroup, 4> : mgx_fused_kernel<V, 1, false, false, false, false, true, false, kGroup, 4>;
-        }
-    }
-    if constexpr (MODE == 3 && !OH && !GEN && V == 7 && !MGX_NO_FIXED_SHAPES) {
-        // the persistent step kernel at the latency shapes (C2 / C4's 8-GPU and 4-GPU shares, C3)
-        switch (match_fixed_shape(ka, hooks, true)) {
-        case 1: kern = ar ? mgx_fused_kernel<V, 3, false, true, false, false, false, false, kGroup, 1> : mgx_fused_kernel<V, 3, false, false, false, false, false, false, kGroup, 1>; break;
-        case 2: kern = ar ? mgx_fused_kernel<V, 3, false, true, false, false, false, false, kGroup, 2> : mgx_fused_kernel<V, 3, false, false, false, false, false, false, kGroup, 2>; break;
-        case 3: kern = ar ? mgx_fused_kernel<V, 3, true, true, false, false, false, false, kGroup, 3> : mgx_fused_kernel<V, 3, true, false, false, false, false, false, kGroup, 3>; break;
-        default: break;
-        }
-    }
-    if constexpr ((MODE == 2 || MODE == 3) && !OH && !GEN && V == 7 && !MGX_NO_FIXED_SHAPES) {
-        // the resident forms of the C4 shape (kShapes 7 / 8: 64 view slots, one or two slices of 16 envs per wavefront)
-        switch (match_resident_shape(ka, hooks)) {
-        case kShapeResident1: kern = ar ? mgx_fused_kernel<V, MODE, false, true, false, false, false, false, kGroup, kShapeResident1>
-                                        : mgx_fused_kernel<V, MODE, false, false, false, false, false, false, kGroup, kShapeResident1>; break;
-        case kShapeResident2: kern = ar ? mgx_fused_kernel<V, MODE, false, true, false, false, false, false, kGroup, kShapeResident2>
-                                        : mgx_fused_kernel<V, MODE, false, false, false, false, false, false, kGroup, kShapeResident2>; break;
-        case kShapeResident4:
-            // (rollouts only.  A persistent launch of 4 x 128 VGPRs per SIMD would leave the producer / consumer kernels of its own
-            // hand-shake no register to run in -- resident_shape() keeps that launch on shapes 7 / 8)
-            if constexpr (MODE == 2) kern = ar ? mgx_resident_kernel<2, true> : mgx_resident_kernel<2, false>;
-            else return MGX_ERR_INVALID_ARGUMENT;
-            break;
-        default: if (ka.ns > 0) return MGX_ERR_INVALID_ARGUMENT;               // (plan_launch chose a geometry no instantiation has)
-        }
-    } else if (ka.ns > 0) return MGX_ERR_INVALID_ARGUMENT;
-    if constexpr (MODE == 1 && !OH && !GEN && GRP == kGroup && !MGX_NO_FIXED_SHAPES) {
-        if (!kern && !occupancy) {
-            if (const JitShape *js = jit_shape_lookup(ka, hooks)) {          // a runtime-compiled instantiation of this very geometry
-                size_t arg_size = sizeof(KernelArgs);
-                void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, const_cast<KernelArgs *>(&ka), HIP_LAUNCH_PARAM_BUFFER_SIZE, &arg_size,
-                                  HIP_LAUNCH_PARAM_END};
-                hipError_t e = hipModuleLaunchKernel(js->fn[ar ? 1 : 0], (unsigned)nwg, 1, 1, (unsigned)threads, 1, 1, (unsigned)lds_bytes,
-                                                     stream, nullptr, config);
-                if (e != hipSuccess) { *hip_err = (int)e; (void)hipGetLastError(); return MGX_ERR_LAUNCH; }
-                return MGX_OK;
-            }
-        }
-    }
-    if (!kern) {
-        if constexpr (MODE == 0 && V <= 7 && !GEN) {
-            kern = mgx_obs_kernel<V, OH, STREAM, DMA>;
-        } else if constexpr (GEN) {                                          // (generation replaces the pool pick-up)
-            if constexpr (DMA) {      // ... and, for BlockedUnlockPickup x 2 (C3 with its episodes generated on the device), its shape
-                const int shape = MGX_NO_FIXED_SHAPES ? 0 : match_fixed_shape(ka, hooks);
-                kern = shape == 3 ? mgx_fused_kernel<V, 1, true, false, false, true, false, true, kGroup, 3>
-                                  : (hooks ? mgx_fused_kernel<V, MODE, S, false, OH, true, false, true> : mgx_fused_kernel<V, MODE, false, false, OH, true, false, true>);
-            } else
-            kern = hooks ? mgx_fused_kernel<V, MODE, S, false, OH, true> : mgx_fused_kernel<V, MODE, false, false, OH, true>;
-        } else {
-            kern = hooks ? (ar ? mgx_fused_kernel<V, MODE, S, S, OH, false, STREAM, DMA, GRP> : mgx_fused_kernel<V, MODE, S, false, OH, false, STREAM, DMA, GRP>)
-                         : (ar ? mgx_fused_kernel<V, MODE, false, S, OH, false, STREAM, DMA, GRP> : mgx_fused_kernel<V, MODE, false, false, OH, false, STREAM, DMA, GRP>);
-        }
-    }
-    return launch_kernel(kern, ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
-}
-
 template <int V>
 inline int launch_view(LaunchForm form, const KernelArgs &ka, int threads, int lds_bytes, int64_t nwg, hipStream_t stream,
                        int *hip_err, int *occupancy) {
-    using F = LaunchForm;
-    switch (form.mode()) {
-    case F::gen_obs().mode(): return launch_mode<V, F::kGenObs, false>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
-    case F::step().mode(): return launch_mode<V, F::kStep, false>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
-    case F::rollout().mode(): return launch_mode<V, F::kRollout, false>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
-    case F::persistent().mode():
-        // (hipcc 7.2 crashes at -O3 on the persistent kernels of the three largest views with the bounds checks / the debug knobs
-        // compiled in.  The checked and the tools' builds compile those units at -O2 (multigrid_amd/build.py: flags) and carry
-        // them; only the single-translation-unit timestamps build, which wants -O3 code for its stamps, leaves them out.)
-        if constexpr (MGX_NO_BIG_PERSIST != 0 && V >= 11) return MGX_ERR_UNSUPPORTED;
-        else return launch_mode<V, F::kPersistent, false>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
-    case F::gen_obs().with_one_hot().mode(): return launch_mode<V, F::kGenObs, true>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
-    case F::step().with_one_hot().mode(): return launch_mode<V, F::kStep, true>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
-    case F::rollout().with_one_hot().mode(): return launch_mode<V, F::kRollout, true>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
-    case F::step().with_generate().mode(): return launch_mode<V, F::kStep, false, true>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
-    case F::step().with_one_hot().with_generate().mode():
-        return launch_mode<V, F::kStep, true, true>(ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
-    default: return MGX_ERR_INVALID_ARGUMENT;      // (no such instantiation: generation is the one-step kernels' tail)
-    }
+    return launch_choice(choose_view<V>(form, ka, occupancy == nullptr), ka, threads, lds_bytes, nwg, stream, hip_err, occupancy);
 }
 
 // One translation unit per view size (mgx_fused_inst.hip, -DMGX_INST_V=<V>) defines its launcher:

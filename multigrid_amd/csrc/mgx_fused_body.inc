@@ -1,6 +1,9 @@
-// mgx_fused_body.inc -- the body of the fused kernel (mgx_fused.h), included textually by its two entry points so that each is
-// compiled exactly as if the body were written in it: mgx_fused_kernel<V, MODE, HOOKS, AR, OH, GEN, STREAM, DMA, GRP, SHAPE, C8> and
-// mgx_obs_kernel<V, OH, STREAM, DMA, C8> (= MODE 0 with an occupancy request).  Expects those names and `a` (KernelArgs).
+// mgx_fused_body.inc -- the body of the fused kernel (mgx_fused.h), included textually by its entry points so that each is compiled
+// exactly as if the body were written in it.  It expects these names in scope, as compile-time constants, and `a` (KernelArgs):
+//     V, MODE, HOOKS, AR, OH, GEN, STREAM, DMA, GRP, SHAPE, C8, B3
+// mgx_fused_kernel takes all twelve as its template parameters, in this order; mgx_obs_kernel (= MODE 0 with an occupancy request),
+// mgx_resident_kernel (= kShapes 9 with one) and the runtime-compiled shape kernels (multigrid_amd/jit.py: source_for) take some and
+// define the rest, in this order too.
     constexpr bool DO_STEP = MODE != 0;
     const int env_kind = HOOKS ? a.sp.env_kind : (int)MGX_KIND_EMPTY;
     constexpr bool PERSIST = MODE == 3;         // persistent stepping: the rollout's step loop, each step's actions handed over as
@@ -9,12 +12,12 @@
     // cache policy of everything a step hands to its consumer: the persistent kernel never ends between steps, so there is no
     // end-of-kernel write-back to make its stores visible -- they are written THROUGH to memory (sc1, aux 16) and the flag
     // follows an s_waitcnt vmcnt(0) (guide: publish/consume recipe R1)
-    constexpr int kOutAux = PERSIST ? 16 : MGX_OUT_AUX;
+    constexpr int kOutAux = PERSIST ? 16 : kSmallOutAux;
     // (base: wave-uniform pointer to the wavefront's first element, idx: this lane's element, n: elements of the wavefront)
 #define MGX_PUB_STORE_U8(base, idx, n, val)                                                                            \
     do {                                                                                                               \
         if constexpr (PERSIST) __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(val), make_rsrc((base), (n)), (idx), 0, 16); \
-        else MGX_STORE_SMALL((base) + (idx), (uint8_t)(val));                                                          \
+        else (base)[idx] = (uint8_t)(val);                                                                           \
     } while (0)
     constexpr int V2 = V * V;
     constexpr int NW = (V2 + 63) / 64;          // 64-bit mask words per view = lane passes per view
@@ -58,10 +61,11 @@
 #define lane lane_
 
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-#if MGX_EARLY_ARGS
     // The kernel arguments P0's load burst needs, fetched in ONE batch of scalar loads at the wavefront's first instructions: left to
     // the compiler they came in four dependent s_load / s_waitcnt pairs, each a scalar-memory round trip in front of the tile burst
-    if constexpr ((DMA || MGX_EARLY_ARGS > 1) && V <= 7) {   // (the latency family: a lone wavefront's instruction chain)
+    // Every instantiation with views <= 7x7: first the latency family only (a lone wavefront's instruction chain), then the C4
+    // throughput kernel too (18.63-18.83 -> 18.45-18.54 us, three same-box passes); 9x9 and up: the compiler crashes on it.
+    if constexpr (V <= 7) {
         const int64_t e_batch = a.batch;
         const uint8_t *e_grid = a.grid, *e_agents = a.agents, *e_aux = a.aux, *e_hord = a.hook_order;
         const uint64_t *e_rng = a.rng;
@@ -75,11 +79,10 @@
         asm volatile("" :: "s"(e_batch), "s"(e_grid), "s"(e_agents), "s"(e_rng), "s"(e_sc), "s"(e_act), "s"(e_hord), "s"(e_aux),
                      "s"(e_bd), "s"(e_ep), "s"(e_trunc), "s"(e_gs), "s"(e_tag));
     }
-#endif
     // SHAPE != 0: an instantiation for ONE (W, H, A, envs per wavefront) of mgx_fused.h's kShapes -- the latency family's answer to
     // what a lone wavefront pays for a runtime shape: every LDS offset of the carve, the agent loops, the row pitch and the
     // lane -> (env, agent) split become immediates (C2: a wave lives 3.78 instead of 4.24 us, BlockedUnlockPickup at 16384
-    // envs 4.45 instead of 5.08; round 3).  The launcher picks it only when the launch geometry matches exactly (launch_mode).
+    // envs 4.45 instead of 5.08; round 3).  The launcher picks it only when the launch geometry matches exactly (choose_in_family).
     constexpr bool FIXED = SHAPE != 0;
     // Two rare-path refinements for big envs (many agents: the shortened sequential fallback; layouts of >= 4 KiB: the vectorised
     // restart copy) are compiled into the one-step kernels for views of 9x9 and more (and the C5 shape) only -- big views are what big
@@ -222,9 +225,8 @@
     const LdsCarve cv = make_carve(W, H, A, V, Gw_, vpw_, ROLL, HOOKS, OH, kR, CB, NS, SLICED, PITCH);
     // bytes between two envs' cells in the TILE (the HBM tensors: HWB)
     const int TSB = PITCH ? PITCH * (H - 1) * CB : HWB;
-    const int wave_lds_ = FIXED ? cv.total() : a.wave_lds;                          // (== the host's wave_lds_bytes: launch_mode checks)
+    const int wave_lds_ = FIXED ? cv.total() : a.wave_lds;                          // (== the host's wave_lds_bytes: match_fixed_shape checks)
     uint8_t *L = lds + wave * wave_lds_;
-    constexpr int kInAux = STREAM ? MGX_IN_AUX : 0;                           // the small state loads of P0
     uint64_t *rows = reinterpret_cast<uint64_t *>(L + cv.rows());             // [slot] packed agent rows
     ViewRec *rec = reinterpret_cast<ViewRec *>(L + cv.rec());                 // [slot]
     int8_t *acts = reinterpret_cast<int8_t *>(L + cv.act());                  // [slot]
@@ -303,7 +305,7 @@
     // Cache is re-read from there by the next step and is best left to the default policy; one that does not is a pure
     // stream and is loaded non-temporal (measured: 1 M envs -3.5 % step / -6.5 % gen_obs and C5 -4 % with nt, C4 +3 %).
     // (A launch-time branch around the two forms cost 3-4 % everywhere: the loads must stay in the straight-line burst.)
-    constexpr int kTileAux = STREAM ? 2 : MGX_TILE_AUX;
+    constexpr int kTileAux = STREAM ? 2 : 0;
     // DMA instantiations: the tile goes HBM -> LDS directly (buffer_load_dwordx4 ... lds: wave-uniform LDS base in M0 + 16
     // bytes per lane, which is exactly the tile's layout): no staging VGPRs (78 instead of 95: the register peak of the
     // step kernel was this burst), no ds_write pass.  Lanes past the wave's bytes are masked off -- an out-of-range lane
@@ -320,9 +322,7 @@
         _Pragma("unroll") for (int u = 0; u < U; ++u)                                                                 \
             dst[u] = __builtin_amdgcn_raw_buffer_load_b128(grsrc, lane16 + 1024 * (u & 3), (base) + 4096 * (u >> 2), kTileAux); \
     }
-#if !MGX_DRAWS_FIRST
     if constexpr (!B3 && PITCH == 0) { MGX_TILE_BURST(tv, 0) }     // (PITCH: the tile is laid out cell by cell, below)
-#endif
     // B3 (byte grids): the first 16 rows of 256 cells -- a C4 wavefront's whole tile -- are requested HERE, with the other formats'
     // tile burst, and converted below once the small inputs are in LDS (round 5's first form issued them after that wait: two
     // memory round trips in a row).  One 12-byte load per lane = 4 cells: a load instruction covers 768 contiguous bytes.
@@ -351,12 +351,8 @@
         uint64_t s_lo, s_hi;
         my_draw = pcg64_draw_at(my_rng, jk, s_lo, s_hi);
         if (GEN) { post_lo = s_lo; post_hi = s_hi; }
-        if (agent_of_lane == A - 1) { uint64_t *dst = a.rng + (e0 + env_of_lane) * 4; MGX_STORE_SMALL(dst, s_lo); MGX_STORE_SMALL(dst + 1, s_hi); }
+        if (agent_of_lane == A - 1) { uint64_t *dst = a.rng + (e0 + env_of_lane) * 4; dst[0] = s_lo; dst[1] = s_hi; }
     }
-#if MGX_DRAWS_FIRST
-    asm volatile("" ::: "memory");
-    if constexpr (!B3 && PITCH == 0) { MGX_TILE_BURST(tv, 0) }
-#endif
     // (3b) big tiles: a second burst under the same wait (requested here, once the draws' inputs are dead, so that the
     // register peak of P0 stays below that of the gather)
     if (big_tile && !B3) {
@@ -388,7 +384,7 @@
         if (lane < Gc) {
             const uint64_t amask = (A >= 64) ? ~0ull : ((1ull << A) - 1ull);
             done = (((alive >> mad24(lane, A, 0)) & amask) == 0) | ((int32_t)in_scnt >= a.sp.max_steps);
-            if (a.was_reset) MGX_STORE_SMALL(a.was_reset + e0 + lane, (uint8_t)done);
+            if (a.was_reset) a.was_reset[e0 + lane] = (uint8_t)done;
         }
         reset_mask0 = __builtin_amdgcn_ballot_w64(done);
     }
@@ -681,14 +677,11 @@
     for (int ts = 0; ts < n_ts; ++ts) {
     const int t = NS > 1 ? (ns_act > 1 ? ts >> 1 : ts) : ts;
     [[maybe_unused]] const int sl_s = NS > 1 ? (ns_act > 1 ? (ts & 1) : 0) : 0;
-#ifndef MGX_ROLL_LAUNDER
-#define MGX_ROLL_LAUNDER 0
-#endif
-    // (-DMGX_ROLL_LAUNDER=1, resident shapes: the lane index is made opaque once per step, so that what is derived from it is
-    // recomputed per step instead of being hoisted out of the loop and held in registers across it: 153 -> 143 VGPRs on the one-slice
-    // kernel -- and 2-3 % SLOWER, same box (profiles/r6_resident.txt): at 12 wavefronts per CU the LDS, not the registers, bounds the
-    // occupancy, so the recomputation buys nothing.  Off.)
-    if constexpr (RSHAPE && (MGX_ROLL_LAUNDER || PITCH != 0)) asm volatile("" : "+v"(lane_));   // (kShapes 9: what makes 127 VGPRs spill-free)
+    // (the ring-sharing resident shape only: the lane index is made opaque once per step, so that what is derived from it is
+    // recomputed per step instead of being hoisted out of the loop and held in registers across it.  On the other resident shapes it
+    // measured 153 -> 143 VGPRs on the one-slice kernel -- and 2-3 % SLOWER, same box (profiles/r6_resident.txt): at 12 wavefronts per
+    // CU the LDS, not the registers, bounds the occupancy, so the recomputation buys nothing.)
+    if constexpr (RSHAPE && PITCH != 0) asm volatile("" : "+v"(lane_));   // (kShapes 9: what makes 127 VGPRs spill-free)
     MGX_SLICE_VARS(sl_s)
     // (PERSIST writes every step's outputs to the same rows.  On the ring-sharing resident shape the offset is made opaque per step:
     // loop-invariant, the ten output descriptors are hoisted out of the step loop and HELD -- 190 spilled SGPRs, which take four
@@ -1036,7 +1029,7 @@
             const int e = lane;
             const int64_t b = e0 + e;
             const int32_t sc = (ROLL ? scnt[e] : (int32_t)in_scnt) + 1;          // base.py:333
-            if (ROLL) scnt[e] = sc; else MGX_STORE_SMALL(p_step_count + b, sc);
+            if (ROLL) scnt[e] = sc; else p_step_count[b] = sc;
             uint8_t *etile = tile + e * TSB;
             uint8_t *ggrid = MGX_LATE(grid) + b * HWG;
             auto dirty = [=](int off) {
@@ -1092,7 +1085,7 @@
         rec[lane] = r;
         if (DO_STEP) {
             const u32x2 rowv = {(uint32_t)row, (uint32_t)(row >> 32)};
-            if (!ROLL) __builtin_amdgcn_raw_buffer_store_b64(rowv, make_rsrc(p_agents + v0 * 8, NVc * 8), lane * 8, 0,MGX_OUT_AUX);
+            if (!ROLL) __builtin_amdgcn_raw_buffer_store_b64(rowv, make_rsrc(p_agents + v0 * 8, NVc * 8), lane * 8, 0, kSmallOutAux);
             const uint64_t rbits = __builtin_bit_cast(uint64_t, my_rew);
             const u32x2 rewv = {(uint32_t)rbits, (uint32_t)(rbits >> 32)};
             __builtin_amdgcn_raw_buffer_store_b64(rewv, make_rsrc(p_reward + tv0, NVc * 8), lane * 8, 0, kOutAux);
@@ -1300,7 +1293,7 @@
                     v.z = (((bits >> 8) & 0xfu) * 0x00204081u) & 0x01010101u;
                     v.w = (((bits >> 12) & 0xfu) * 0x00204081u) & 0x01010101u;
                     if ((rel + 16 <= rlen) & (rel >= oh_skew)) {
-                        __builtin_amdgcn_raw_buffer_store_b128(v, orsrc, rel, 0, PERSIST ? 16 : MGX_OH_AUX);
+                        __builtin_amdgcn_raw_buffer_store_b128(v, orsrc, rel, 0, PERSIST ? 16 : kOhAux);
                     } else {                                                    // ragged head / tail of the wave's bytes
                         const int lo_b = max(rel, oh_skew), hi_b = min(rel + 16, rlen);
 #pragma clang loop vectorize(disable) unroll(disable)
@@ -1351,7 +1344,7 @@
             obs_unit(0u, d[k].x, d[k].y, d[k].z, d[k].w, 0, w);
             if (64 * (k + 1) <= kWhole || lane + 64 * k < kWhole)
                 __builtin_amdgcn_raw_buffer_store_b96(u32x3{w[0], w[1], w[2]}, orsrc, 12 * (lane + 64 * k), r0 * V2 * 3,
-                                                      STREAM ? MGX_OBS_AUX : MGX_OBS_AUX_CACHED);
+                                                      kObsAux);
         }
     };
     // P5 of any round at r0 (a wave's last, partial one; a wave whose bytes start s = s_w bytes into a dword)
@@ -1368,7 +1361,7 @@
                 uint32_t w[3];
                 obs_unit(dm1, d.x, d.y, d.z, d.w, s, w);
                 if (ub >= s && ub + 12 <= ulen) {
-                    __builtin_amdgcn_raw_buffer_store_b96(u32x3{w[0], w[1], w[2]}, orsrc, ub, roff, STREAM ? MGX_OBS_AUX : MGX_OBS_AUX_CACHED);
+                    __builtin_amdgcn_raw_buffer_store_b96(u32x3{w[0], w[1], w[2]}, orsrc, ub, roff, kObsAux);
                 } else {                                                        // the ragged head / tail of the round's bytes
                     const int lo_b = max(s - ub, 0), hi_b = min(ulen - ub, 12);
 #pragma clang loop vectorize(disable) unroll(disable)
@@ -1573,18 +1566,14 @@
                     const int rel = lane16 + 1024 * k;
                     if (rel < rlen) MGX_CHECK_LDS_PTR(6, out_raw + rel, 16);
                     if ((rel + 16 <= rlen) & (rel >= out_skew)) {
-#if MGX_BUF_STORE
                         __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4 *>(out_raw + rel), orsrc, rel, 0,
-                                                               PERSIST ? 16 : (STREAM ? MGX_OBS_AUX : MGX_OBS_AUX_CACHED));
-#else
-                        *reinterpret_cast<u32x4 *>(gdst + rel) = *reinterpret_cast<const u32x4 *>(out_raw + rel);
-#endif
+                                                               PERSIST ? 16 : kObsAux);
                     } else if (rel < rlen) {                                    // ragged head / tail of the wave's bytes
                         const int lo_b = max(rel, out_skew), hi_b = min(rel + 16, rlen);
                         if ((kRoundBytes & 15) != 0 && ((lo_b | hi_b) & 7) == 0) {
                             // (rounds of 8 slots: the round's last / first HALF vector -- every round of a full slice has one)
                             __builtin_amdgcn_raw_buffer_store_b64(*reinterpret_cast<const u32x2 *>(out_raw + lo_b), orsrc, lo_b, 0,
-                                                                  PERSIST ? 16 : MGX_OBS_AUX_CACHED);
+                                                                  PERSIST ? 16 : kObsAux);
                         } else {
 #pragma clang loop vectorize(disable) unroll(disable)
                             for (int B = lo_b; B < hi_b; ++B) __builtin_amdgcn_raw_buffer_store_b8(out_raw[B], orsrc, B, 0, PERSIST ? 16 : 0);

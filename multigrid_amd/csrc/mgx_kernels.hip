@@ -259,7 +259,7 @@ int check_auto_reset(const MgxSpec &sp, const MgxAutoReset &ar) {
     return MGX_OK;
 }
 
-// A non-null ka.pool_grid is what selects the instantiations WITH the fused auto-reset (mgx_fused.h: launch_mode, `ar`).
+// A non-null ka.pool_grid is what selects the instantiations WITH the fused auto-reset (mgx_fused.h: choose_in_family, `ar`).
 // `occupancy`: the plan is for an occupancy query, which checks no pointer and launches nothing but must ask about the kernel the
 // launch will run: a null pool_grid is stood in for by the spec's address.
 void bind_auto_reset(KernelArgs &ka, const MgxSpec *spec, const MgxAutoReset &ar, const int *occupancy = nullptr) {

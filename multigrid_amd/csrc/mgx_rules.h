@@ -177,19 +177,8 @@ MGX_HD uint32_t cell_pack(uint32_t c) {
 // what a cell SHOWS (observations, full_obs): (type, color, state)
 MGX_HD uint32_t cell_unpack(uint32_t p) { return (p & 0x070fu) | ((p & 0x3000u) << 4); }
 // ... and with a box's content, for the rules
-// (-DMGX_BOX_CONTENTS=0 / -DMGX_RULES_KIND=0: A/B builds without the round-5 additions to the per-agent phase, tools/variant_bench.sh)
-#ifndef MGX_BOX_CONTENTS
-#define MGX_BOX_CONTENTS 1
-#endif
-#ifndef MGX_RULES_KIND
-#define MGX_RULES_KIND 1
-#endif
 MGX_HD uint32_t cell_unpack_full(uint32_t p) {
-#if MGX_BOX_CONTENTS
     return cell_unpack(p) | ((p & 0x00f0u) << 14) | ((p & 0x0800u) << 11) | ((p & 0x4000u) << 9);
-#else
-    return cell_unpack(p);
-#endif
 }
 // the agent overlay cell (10, color, dir) of a packed agent row (obs.py:163-173); never opaque
 MGX_HD uint32_t agent_cell16(uint64_t row) {
@@ -650,7 +639,6 @@ MGX_HD void post_step_hook(const StepCfg &cf, int env_kind, uint8_t *tile, uint6
         int cnt = 0;
         for (int k = 0; k < nd; ++k) cnt += (mask >> k) & 1u;
         aux[15] = (uint8_t)(cnt == target);      // len(unlocked_doors) == len(rooms): `terminations` only, not agent state
-#if MGX_RULES_KIND
     } else if (env_kind == MGX_KIND_RULES) {
         // the declared hook of a user-defined env (include/mgx.h: MGX_KIND_RULES): rule by rule in table order
         const int n = aux[0] < MGX_MAX_RULES ? aux[0] : MGX_MAX_RULES;
@@ -679,7 +667,6 @@ MGX_HD void post_step_hook(const StepCfg &cf, int env_kind, uint8_t *tile, uint6
                 else if (effect == MGX_EFFECT_FAILURE) set_terminated(rows, A, a, cf.failure_any);
             }
         }
-#endif
     }
 }
 

@@ -49,13 +49,16 @@ def shape_key(spec: EnvSpec, batch: int) -> MgxShapeKey:
 
 def source_for(key: MgxShapeKey) -> str:
     """The translation unit: the library's own kernel body, instantiated for one launch geometry (csrc/mgx_fused.h: kShapes'
-    MGX_JIT_SHAPE entry), as two extern "C" kernels -- the plain step without / with the fused auto-reset."""
+    MGX_JIT_SHAPE entry), as two extern "C" kernels -- the plain step without / with the fused auto-reset.  Each defines the names
+    the body expects, in the order its header comment lists them (csrc/mgx_fused_body.inc)."""
     b = lambda v: "true" if v else "false"
     init = f"{key.width}, {key.height}, {key.num_agents}, {key.envs_per_wavefront}, {b(key.hooks)}, {key.view_size}, {b(key.dma)}, {b(key.stream)}"
     kern = """
 extern "C" __global__ __launch_bounds__(kMaxThreads) void %s(const KernelArgs a) {
-    constexpr int V = %d, MODE = 1, GRP = kGroup, SHAPE = kNumShapes - 1;
-    constexpr bool HOOKS = %s, AR = %s, OH = false, GEN = false, STREAM = %s, DMA = %s, C8 = false, B3 = false;
+    constexpr int V = %d, MODE = 1;
+    constexpr bool HOOKS = %s, AR = %s, OH = false, GEN = false, STREAM = %s, DMA = %s;
+    constexpr int GRP = kGroup, SHAPE = kNumShapes - 1;
+    constexpr bool C8 = false, B3 = false;
 #include "mgx_fused_body.inc"
 }
 """

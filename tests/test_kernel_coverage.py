@@ -20,3 +20,17 @@ def test_every_shipped_kernel_was_launched_by_the_gpu_suite():
     assert not missing, (f"{len(missing)} kernel(s) in libmgx.so were never launched by the GPU suite (add a case to "
                          f"tests/test_instantiations.py, re-run tools/kernel_coverage.py run, or drop the instantiation): {missing[:12]}")
     assert len(ok) <= 12, "the exceptions are meant to stay a short, argued list"
+
+
+def test_every_launched_fused_kernel_is_still_in_the_library():
+    """The other direction, for the fused kernel's three entry points: a name on the committed list that the library no longer
+    carries means a host-side change of the selection code lost or renamed an instantiation -- the launch that used to reach it now
+    runs another kernel with the same results, which no parity test can see."""
+    from multigrid_amd import build
+    build.build_lib()
+    ship, got = kc.shipped(), kc.read_list(kc.LAUNCHED)
+    fused = sorted(n for n in got if n.startswith(("mgx_fused::mgx_fused_kernel<", "mgx_fused::mgx_obs_kernel<",
+                                                   "mgx_fused::mgx_resident_kernel<")))
+    assert len(fused) > 300, "profiles/kernels_launched.txt is missing or truncated"
+    lost = [n for n in fused if n not in ship]
+    assert not lost, f"{len(lost)} kernel(s) the GPU suite launched are no longer in libmgx.so: {lost[:12]}"

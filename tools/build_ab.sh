@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B library: lib/libmgx_ab.so = the product library's objects with the 7x7 instantiation unit recompiled with extra defines
-#   tools/build_ab.sh -DMGX_ROLL_LAUNDER=0 ...      then   MGX_LIBMGX=multigrid_amd/lib/libmgx_ab.so python tools/...
+#   tools/build_ab.sh -DMGX_NO_FIXED_SHAPES=1 ...      then   MGX_LIBMGX=multigrid_amd/lib/libmgx_ab.so python tools/...
 set -e
 cd "$(dirname "$0")/.."
 OBJ=build/libmgx.so.obj
