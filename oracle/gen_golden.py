@@ -25,6 +25,8 @@ Array conventions in the .npz files (reference layouts, narrowed to the smallest
                  lay_before / npr_before / lay_after / npr_after u64[N,5], grid0 u8[N,H,W,3], agents0 u8[N,A,8], obs0, target,
                  lay_halves / npr_halves, and the instrumentation tables calls / resamples / shuffles / key_draws / object_rooms
                  (see record_resets' docstring)
+    conflict_*.npz (record_conflicts: constructed envs in which the visiting order decides the outcome) hold the arrays of
+                 randstate_*.npz (record_random_states' docstring) and order / scenario / cluster_agents / cluster_block
     hook_order   (T,A) u8, only in the *_dictorder fixtures: the insertion order of the keys of the actions dict handed to
                  step() at step t (the RedBlueDoors / LockedHallway hooks iterate actions.items(), redbluedoors.py:176,
                  locked_hallway.py:210); every other fixture builds its dict in ascending agent order
@@ -332,6 +334,7 @@ def main():
     record_resets()          # (likewise; both generators' states are set before every recorded reset)
     record_reset_chains()
     record_lh_12rooms()      # (a construction seed of its own: nothing above moves)
+    record_conflicts()       # (constructs no registered env either)
 
 
 def face(env, i, target_xy, carrying=None):
@@ -940,6 +943,265 @@ def record_random_states():
     assert total <= 1 << 20, "the random-state corpus must stay within 1 MiB"
 
 
+# ---- the conflict corpus (tests/golden/conflict_*.npz): constructed envs in which the visiting order decides the outcome ----------
+#: (file, EnvSpec keywords, boxes that hold something)
+CONFLICT_SPECS = [
+    ("conflict_9x6_a2_v5", dict(width=9, height=6, num_agents=2, view_size=5, max_steps=12, allow_agent_overlap=False,
+                                failure_termination_mode="any"), False),
+    ("conflict_16x16_a4_v7", dict(width=16, height=16, num_agents=4, view_size=7, max_steps=20), False),      # the C2 / C4 shape
+    ("conflict_10x8_a3_v7", dict(width=10, height=8, num_agents=3, view_size=7, max_steps=14, allow_agent_overlap=False,
+                                 joint_reward=True, success_termination_mode="all", failure_termination_mode="any"), False),
+    ("conflict_13x10_a5_v9", dict(width=13, height=10, num_agents=5, view_size=9, max_steps=200, allow_agent_overlap=False,
+                                  success_termination_mode="all"), False),
+    ("conflict_20x14_a16_v9", dict(width=20, height=14, num_agents=16, view_size=9, max_steps=65535, joint_reward=True,
+                                   failure_termination_mode="any"), False),
+    ("conflict_bup_11x6_a2_v7", dict(width=11, height=6, num_agents=2, view_size=7, max_steps=16, joint_reward=True,
+                                     env_kind="blockedunlockpickup"), False),
+    ("conflict_10x8_a3_v7_boxes", dict(width=10, height=8, num_agents=3, view_size=7, max_steps=40), True),
+    ("conflict_64x64_a16_v9", dict(width=64, height=64, num_agents=16, view_size=9, max_steps=4 * 64 * 64), False),   # the C5 shape
+]
+CONFLICT_INSTANCES = 8          # per scenario and file, before the batch is padded to its size
+
+_E, _S, _W, _N = 0, 1, 2, 3     # agent directions (agent.py:111-118)
+_LEFT, _FWD, _PICK, _DROP, _TOG = 0, 2, 3, 4, 5
+_KEY, _BALL, _BOX, _GOAL, _LAVA = (5, 2, 0), (6, 1, 0), (7, 3, 0), (8, 1, 0), (9, 0, 0)
+_BOX_KEY = (7, 3, (1 | 2 << 3) << 2)            # a box that holds a blue key / a floor tile (include/mgx.h "BOX CONTENTS")
+_BOX_FLOOR = (7, 3, (4 | 0 << 3) << 2)
+_OPEN, _CLOSED, _LOCKED = (4, 2, 0), (4, 2, 1), (4, 2, 2)
+_BUP_TARGET = (7, 4, 0)                         # the one box BlockedUnlockPickup pays for; every other box above is purple
+
+
+def _noovl(kw):
+    return not kw.get("allow_agent_overlap", True)
+
+
+#: The scenario table.  A scenario lives in a block of 4 x 2 cells; positions are (dx, dy) inside it.
+#: (name, {cell: (type, colour, state)}, [(position, direction, carried cell or None, action)], admitted(spec keywords, boxes), event class)
+#: event class: 0 none, 1 an event and a second agent with an effective action, 2 an event beside a cell conflict
+#: Agents 0 and 1 of a row are the pair whose relative visiting order the recorder balances.
+#: Not in the table, because the reference's outcome does not depend on the visiting order (the recorder's assertion fails on them):
+#:   wrong key x forward              -- Door.toggle with another colour's key changes nothing, the forward is refused either way
+#:   forward into a terminated agent  -- the terminated agent never moves, the forward is refused either way
+#:   toggle x toggle on a closed door -- closed again in both orders; the row below is a LOCKED door and one matching key instead
+#:   goal / lava under mode 'all' with agent overlap allowed -- the event ends only its own agent, nobody's inputs change; under
+#:     'all' the event rows are the *_shared ones (two agents, one cell, no overlap)
+CONFLICT_SCENARIOS = [
+    # cell conflicts
+    ("pickup_pickup", {(1, 0): _KEY}, [((0, 0), _E, None, _PICK), ((2, 0), _W, None, _PICK)], lambda kw, bx: True, 0),
+    ("pickup_forward", {(1, 0): _KEY}, [((0, 0), _E, None, _PICK), ((2, 0), _W, None, _FWD)], lambda kw, bx: True, 0),
+    ("drop_forward", {}, [((0, 0), _E, _BALL, _DROP), ((2, 0), _W, None, _FWD)], lambda kw, bx: True, 0),
+    ("drop_drop", {}, [((0, 0), _E, _BALL, _DROP), ((2, 0), _W, _KEY, _DROP)], lambda kw, bx: True, 0),
+    ("drop_pickup", {}, [((0, 0), _E, _BALL, _DROP), ((2, 0), _W, None, _PICK)], lambda kw, bx: True, 0),
+    ("toggle_open_forward", {(1, 0): _OPEN}, [((0, 0), _E, None, _TOG), ((2, 0), _W, None, _FWD)], lambda kw, bx: True, 0),
+    ("toggle_closed_forward", {(1, 0): _CLOSED}, [((0, 0), _E, None, _TOG), ((2, 0), _W, None, _FWD)], lambda kw, bx: True, 0),
+    ("toggle_toggle", {(1, 0): _LOCKED}, [((0, 0), _E, _KEY, _TOG), ((2, 0), _W, None, _TOG)], lambda kw, bx: True, 0),
+    ("unlock_forward", {(1, 0): _LOCKED}, [((0, 0), _E, _KEY, _TOG), ((2, 0), _W, None, _FWD)], lambda kw, bx: True, 0),
+    ("togglebox_pickup", {(1, 0): _BOX}, [((0, 0), _E, None, _TOG), ((2, 0), _W, None, _PICK)], lambda kw, bx: True, 0),
+    ("togglebox_forward", {(1, 0): _BOX}, [((0, 0), _E, None, _TOG), ((2, 0), _W, None, _FWD)], lambda kw, bx: True, 0),
+    ("togglefilled_pickup", {(1, 0): _BOX_KEY}, [((0, 0), _E, None, _TOG), ((2, 0), _W, None, _PICK)], lambda kw, bx: bx, 0),
+    ("togglefilled_forward", {(1, 0): _BOX_FLOOR}, [((0, 0), _E, None, _TOG), ((2, 0), _W, None, _FWD)], lambda kw, bx: bx, 0),
+    ("pickupfilled_pickup", {(1, 0): _BOX_KEY}, [((0, 0), _E, None, _PICK), ((2, 0), _W, None, _PICK)], lambda kw, bx: bx, 0),
+    ("pickup_pickup_target", {(1, 0): _BUP_TARGET}, [((0, 0), _E, None, _PICK), ((2, 0), _W, None, _PICK)],
+     lambda kw, bx: kw.get("env_kind") == "blockedunlockpickup", 0),
+    # presence
+    ("forward_forward_one_cell", {}, [((0, 0), _E, None, _FWD), ((2, 0), _W, None, _FWD)], lambda kw, bx: _noovl(kw), 0),
+    ("forward_into_vacated", {}, [((0, 0), _E, None, _FWD), ((1, 0), _E, None, _FWD)], lambda kw, bx: _noovl(kw), 0),
+    ("line_of_three", {}, [((0, 0), _E, None, _FWD), ((1, 0), _E, None, _FWD), ((2, 0), _E, None, _FWD)],
+     lambda kw, bx: _noovl(kw), 0),
+    ("drop_before_arriving", {}, [((0, 0), _E, _BALL, _DROP), ((1, 1), _N, None, _FWD)], lambda kw, bx: True, 0),
+    ("drop_behind_leaving", {}, [((0, 0), _E, _BALL, _DROP), ((1, 0), _E, None, _FWD)], lambda kw, bx: True, 0),
+    # events: the second agent holds an effective action
+    ("goal_other_acts", {(1, 0): _GOAL}, [((0, 0), _E, None, _FWD), ((0, 1), _E, None, _FWD)],
+     lambda kw, bx: kw.get("success_termination_mode", "any") == "any", 1),
+    ("lava_other_acts", {(1, 0): _LAVA}, [((0, 0), _E, None, _FWD), ((0, 1), _E, None, _FWD)],
+     lambda kw, bx: kw.get("failure_termination_mode", "all") == "any", 1),
+    ("goal_shared", {(1, 0): _GOAL}, [((0, 0), _E, None, _FWD), ((2, 0), _W, None, _FWD)], lambda kw, bx: _noovl(kw), 1),
+    ("lava_shared", {(1, 0): _LAVA}, [((0, 0), _E, None, _FWD), ((2, 0), _W, None, _FWD)], lambda kw, bx: _noovl(kw), 1),
+    # ... inside an env that also has a cell conflict: the event is the sequential loop's
+    ("goal_beside_conflict", {(1, 0): _KEY, (1, 1): _GOAL},
+     [((0, 0), _E, None, _PICK), ((2, 0), _W, None, _FWD), ((0, 1), _E, None, _FWD)], lambda kw, bx: True, 2),
+    ("lava_beside_conflict", {(1, 0): _KEY, (1, 1): _LAVA},
+     [((0, 0), _E, None, _PICK), ((2, 0), _W, None, _FWD), ((0, 1), _E, None, _FWD)], lambda kw, bx: True, 2),
+]
+
+
+def _order_of(words, A):
+    """The visiting order handle_actions draws (base.py:396-399) from the generator state `words` (product order)."""
+    bg = np.random.PCG64()
+    st = bg.state
+    st["state"] = {"state": int(words[0]) | (int(words[1]) << 64), "inc": int(words[2]) | (int(words[3]) << 64)}
+    st["has_uint32"], st["uinteger"] = 0, 0
+    bg.state = st
+    return np.random.Generator(bg).random(size=A).argsort()
+
+
+def _conflict_batch(kw, boxes):
+    """The envs of one file: lists of (scenario row, instance number) packed into the spec's A agents, events in envs of their own
+    (an ends-all event would blur the other scenarios' own order dependence); then padded until the batch is odd and no multiple
+    of any number of envs a wavefront can hold (one lane per agent: at most 64 // A)."""
+    A, W, H = kw["num_agents"], kw["width"], kw["height"]
+    rows = [sc for sc in CONFLICT_SCENARIOS if sc[3](kw, boxes) and len(sc[2]) <= A]
+    envs = []
+
+    def pack(instances, most):
+        cur, used = [], 0
+        for sc, k in instances:
+            n = len(sc[2])
+            if used + n > A or len(cur) == most:
+                envs.append(cur)
+                cur, used = [], 0
+            cur.append((sc, k))
+            used += n
+        if cur:
+            envs.append(cur)
+
+    pack([(sc, k) for k in range(CONFLICT_INSTANCES) for sc in rows if sc[4] == 0], 8)
+    # an event alone in its env, three times as often: only where nothing else forces the sequential loop does the EVENT CUTOFF of
+    # the order-free path decide who acts, and only in half of the orders does it suppress anybody
+    pack([(sc, k) for k in range(3 * CONFLICT_INSTANCES) for sc in rows if sc[4] == 1], 1)
+    pack([(sc, k) for k in range(CONFLICT_INSTANCES) for sc in rows if sc[4] == 2], 2)
+    k = CONFLICT_INSTANCES
+    while len(envs) % 2 == 0 or any(len(envs) % g == 0 for g in range(2, 64 // A + 1)):
+        n0 = len(envs)
+        pack([(sc, k) for sc in rows], 8)
+        del envs[n0 + 1:]
+        k += 1
+    return rows, envs
+
+
+def record_conflicts():
+    """Every spec of CONFLICT_SPECS: envs BUILT so that the visiting order decides the outcome -- every row of CONFLICT_SCENARIOS the
+    spec admits, CONFLICT_INSTANCES times, from generator states chosen so that the row's first two agents are visited in either
+    order -- each loaded into the reference (_loaded_env) and stepped twice with the row's actions.  The recorder ASSERTS, per file
+    and row, that two distinct visiting orders occurred and that the reference's post-step state or outputs differ between them.
+
+    Arrays: exactly those of record_random_states, and
+        order u8[T,B,A]        the visiting order of each step         scenario str[B]    the rows an env holds, '+'-joined
+        cluster_agents i8[B,8,3], cluster_block u8[B,8,2]   per env and cluster: its agents (-1 = none), its block's (x, y)"""
+    sys.path.insert(0, REPO)
+    from multigrid_amd import layouts
+    from multigrid_amd.spec import EnvSpec
+    total = 0
+    T = 2
+    for n, (fname, kw, boxes) in enumerate(CONFLICT_SPECS):
+        spec = EnvSpec(**kw)
+        sd = spec.as_dict()
+        A, W, H = spec.num_agents, spec.width, spec.height
+        bup = spec.env_kind == "blockedunlockpickup"
+        rows_admitted, envs = _conflict_batch(kw, boxes)
+        B = len(envs)
+        assert B % 2 == 1 and all(B % g for g in range(2, 64 // A + 1)), B
+        across = (W - 2) // 4
+        r = np.random.default_rng(9000 + n)
+        grid = np.zeros((B, H, W, 3), np.uint8)
+        grid[..., 0] = 1
+        grid[:, 0, :] = grid[:, -1, :] = grid[:, :, 0] = grid[:, :, -1] = (2, 5, 0)
+        agents = np.zeros((B, A, 8), np.uint8)
+        agents[..., 0] = np.arange(A) % 6
+        agents[..., 5] = 1
+        rng = np.zeros((B, 4), np.uint64)
+        actions = np.zeros((T, B, A), np.int8)
+        cl_agents = np.full((B, 8, 3), -1, np.int8)
+        cl_block = np.zeros((B, 8, 2), np.uint8)
+        aux = np.zeros((B, 16), np.uint8)
+        targets = [None] * B
+        step_count = (np.arange(B) % max(1, spec.max_steps - T)).astype(np.int32)
+        for b, env in enumerate(envs):
+            a, want = 0, []
+            for c, (sc, k) in enumerate(env):
+                bx, by = 1 + 4 * (c % across), 1 + 2 * (c // across)
+                cl_block[b, c] = bx, by
+                for (dx, dy), cell in sc[1].items():
+                    grid[b, by + dy, bx + dx] = cell
+                    if cell == _BUP_TARGET:
+                        targets[b] = ("grid", bx + dx, by + dy)
+                for j, ((dx, dy), d, carry, action) in enumerate(sc[2]):
+                    agents[b, a, 1:4] = d, bx + dx, by + dy
+                    agents[b, a, 5:8] = carry if carry is not None else (1, 0, 0)
+                    actions[:, b, a] = action
+                    cl_agents[b, c, j] = a
+                    a += 1
+                i0 = a - len(sc[2])
+                want.append((i0, i0 + 1, bool(k & 1)))
+                if sc[4] == 2:                           # the event's agent ahead of the conflicting pair, or behind one of them
+                    want.append((i0 + 2, i0 if k & 1 else i0 + 1, bool(k & 2)))
+            c = len(env)
+            for j in range(A - a):                       # the agents no row uses turn on the spot, in blocks of their own
+                cj = c + j // 8
+                agents[b, a + j, 1:4] = _N, 1 + 4 * (cj % across) + j % 4, 1 + 2 * (cj // across) + j % 8 // 4
+                actions[:, b, a + j] = _LEFT
+            assert len(env) <= 8 and c + (A - a + 7) // 8 <= across * ((H - 2) // 2), "the grid has too few blocks"
+            if bup:
+                aux[b, :3] = _BUP_TARGET
+            while True:                                      # a generator state under which every pair is visited as wanted
+                w = r.integers(0, 2 ** 63, size=4, dtype=np.int64).astype(np.uint64)
+                w[2] |= np.uint64(1)
+                rank = np.argsort(_order_of(w, A))
+                if all((rank[i] < rank[j]) == first for i, j, first in want):
+                    break
+            rng[b] = w
+        st = dict(grid=grid, agents=agents, rng=rng, step_count=step_count, target=aux)
+        rec = dict(grid0=grid, agents0=agents, rng0=rng, step_count0=step_count, aux=aux, actions=actions,
+                   cluster_agents=cl_agents, cluster_block=cl_block,
+                   scenario=np.array(["+".join(sc[0] for sc, _ in env) for env in envs]))
+        keys = ("obs", "dir", "reward", "terminated", "truncated", "grid", "agents", "rng", "order")
+        log = {k: [[None] * B for _ in range(T)] for k in keys}
+        obs0, dir0 = [], []
+        for b in range(B):
+            env = _loaded_env(sd, st, b, targets[b])
+            assert (layouts.grid_to_product(grid_with_contents(env)) == grid[b]).all()
+            assert (layouts.pack_agents(agents_with_contents(env)) == agents[b]).all()
+            o = env.gen_obs()
+            obs0.append(np.stack([o[i]["image"] for i in range(A)]))
+            dir0.append([int(o[i]["direction"]) for i in range(A)])
+            for t in range(T):
+                log["order"][t][b] = clone_order(env.np_random, A)
+                o, rew, term, trunc, _ = env.step({i: int(x) for i, x in enumerate(actions[t, b])})
+                log["obs"][t][b] = np.stack([o[i]["image"] for i in range(A)])
+                log["dir"][t][b] = [int(o[i]["direction"]) for i in range(A)]
+                log["reward"][t][b] = [float(rew[i]) for i in range(A)]
+                log["terminated"][t][b] = [bool(term[i]) for i in range(A)]
+                log["truncated"][t][b] = bool(trunc[0])
+                log["grid"][t][b] = layouts.grid_to_product(grid_with_contents(env))
+                log["agents"][t][b] = layouts.pack_agents(agents_with_contents(env))
+                log["rng"][t][b] = _product_rng(env.np_random)
+            assert (log["order"][0][b] == _order_of(rng[b], A)).all()
+        rec["obs0"] = np.asarray(obs0).astype(np.uint8)
+        rec["dir0"] = np.asarray(dir0).astype(np.uint8)
+        for k in keys:
+            arr = np.asarray(log[k])
+            rec[k] = arr.astype(np.float64) if k == "reward" else arr if k == "rng" else arr.astype(np.uint8)
+        # order sensitivity, row by row: the first step's outcome INSIDE the cluster (its agents' rows without the colour byte, its
+        # block's cells, who was paid, who is terminated), keyed by the relative visiting order of the cluster's agents
+        for sc in rows_admitted:
+            seen = {}
+            for b, env in enumerate(envs):
+                if not sc[4] and any(other[4] for other, _ in env):
+                    continue                             # (a padding env that mixes this row with an event)
+                for c, (other, _) in enumerate(env):
+                    if other is not sc:
+                        continue
+                    ag = [int(i) for i in cl_agents[b, c] if i >= 0]
+                    rank = np.argsort(rec["order"][0, b])
+                    key = tuple(np.argsort([rank[i] for i in ag]))
+                    bx, by = (int(v) for v in cl_block[b, c])
+                    out = (rec["agents"][0, b, ag, 1:].tobytes(), rec["grid"][0, b, by:by + 2, bx:bx + 4].tobytes(),
+                           (rec["reward"][0, b, ag] > 0).tobytes(), rec["terminated"][0, b, ag].tobytes())
+                    seen.setdefault(key, set()).add(out)
+            assert len(seen) >= 2, f"{fname} {sc[0]}: one visiting order only"
+            outs = list(seen.values())
+            assert any(x != y for i, x in enumerate(outs) for y in outs[i + 1:]), \
+                f"{fname} {sc[0]}: the reference's outcome does not depend on the visiting order"
+        rec["spec_json"] = np.array(json.dumps(dict(sd, conflict_rows=[sc[0] for sc in rows_admitted], seed=9000 + n)))
+        path = os.path.join(OUT, fname + ".npz")
+        np.savez_compressed(path, **rec)
+        total += os.path.getsize(path)
+        print(f"{fname:30s} B={B:3d} T={T} rows={len(rows_admitted):2d} success-steps={int((rec['reward'] > 0).any(axis=2).sum()):4d} "
+              f"{os.path.getsize(path) / 1024:.1f} KiB")
+    print(f"conflict corpus: {total / 1024:.1f} KiB")
+    assert total <= 512 << 10, "the conflict corpus must stay within 512 KiB"
+
+
 # ---- the reset corpus (tests/golden/resets_*.npz): single resets of the REAL reference from given generator states ---------------
 #: (file tag, generator kind of the product, reference class name, constructor keywords, events)
 RESET_CONFIGS = [
@@ -1372,5 +1634,7 @@ def spec_of_noreset(env, kind):
 if __name__ == "__main__":
     if sys.argv[1:] == ["lh_12rooms"]:
         record_lh_12rooms()
+    elif sys.argv[1:] == ["conflicts"]:
+        record_conflicts()
     else:
         main()

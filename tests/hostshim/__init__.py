@@ -38,9 +38,22 @@ def _layouts():
     return layouts
 
 
-def step_env(spec, tile, rows8, act, rng4, step_count, target, force_serial=False, hook_order=None):
+FORMS = {"prefix": 0, "first": 1}
+PATH_PAIRS = 64
+
+
+def step_env(spec, tile, rows8, act, rng4, step_count, target, force_serial=False, hook_order=None, form="prefix", path=False):
     """tile u8[H,W,3], rows8 u8[A,8], act i8[A], rng4 u64[4], target = aux u8[16]; all updated in place.
-    Returns dict(obs, reward, terminated, truncated, order, rc, n_dirty)."""
+    Returns dict(obs, reward, terminated, truncated, order, rc, n_dirty).
+
+    form: which of the kernel's two fallback commits is modelled (mgx_fused_body.inc, P1s): "prefix" -- the agents ranked below the
+    first blocked one commit with their order-free results (the kernels with PREFIX, at A > 2); "first" -- only the agent visited
+    first commits early, and only without an unknown action or an event (every other kernel, and every kernel at A <= 2).
+    path=True adds `path` to the result: what the decision logic did for this env --
+        fallback (bool), why (set of "bad", "conflict", "presence", "forced"), ends_all / ends_self (an event of that kind in the
+        order-free evaluation), event_cutoff (rank, None without one) and suppressed (agents with an effective action -- one that
+        would have moved, turned or written -- behind it) in the no-fallback branch, commit_cutoff (the rank the sequential loop
+        starts at; None without fallback), pairs: [(writer's action, reader's action, front cell type, its state, box holds something)]."""
     sc = spec.to_c()
     A, v = spec.num_agents, spec.view_size
     # the rules work on packed cells (include/mgx.h MgxCell, or MgxCell8 for spec.cell_bytes == 1); the tests speak (type, color,
@@ -51,17 +64,28 @@ def step_env(spec, tile, rows8, act, rng4, step_count, target, force_serial=Fals
     rew = np.empty(A, np.float64); term = np.empty(A, np.uint8); trunc = np.zeros(1, np.uint8)
     order = np.empty(A, np.uint8); nd = C.c_int32(0); scnt = C.c_int32(int(step_count))
     rows = rows8.view(np.uint64).reshape(A)
+    pw = np.zeros(8 + 4 * PATH_PAIRS, np.int32) if path else None
     rc = lib().shim_step_env(C.byref(sc), _p(tile, C.c_uint8), _p(over, C.c_uint8), _p(rows, C.c_uint64),
                              _p(act, C.c_int8), _p(rng4, C.c_uint64), C.byref(scnt), _p(target, C.c_uint8),
                              _p(rew, C.c_double), _p(term, C.c_uint8), _p(trunc, C.c_uint8), _p(order, C.c_uint8),
                              C.byref(nd), int(force_serial),
-                             _p(np.ascontiguousarray(hook_order, dtype=np.uint8), C.c_uint8) if hook_order is not None else None)
+                             _p(np.ascontiguousarray(hook_order, dtype=np.uint8), C.c_uint8) if hook_order is not None else None,
+                             FORMS[form], _p(pw, C.c_int32) if path else None)
     obs = np.empty((A, v, v, 3), np.uint8)
     assert lib().shim_obs_env(C.byref(sc), _p(over, C.c_uint8), _p(rows, C.c_uint64), _p(obs, C.c_uint8)) == 0
     assert np.array_equal(L.pack_cells_for(spec, L.unpack_cells_for(spec, tile)), tile), "opaque bits out of date"
     tile3[...] = L.unpack_cells_for(spec, tile)
-    return dict(obs=obs, reward=rew, terminated=term, truncated=int(trunc[0]), order=order, rc=rc,
-                n_dirty=nd.value, step_count=scnt.value, serial=nd.value < 0)
+    out = dict(obs=obs, reward=rew, terminated=term, truncated=int(trunc[0]), order=order, rc=rc,
+               n_dirty=nd.value, step_count=scnt.value, serial=nd.value < 0)
+    if path:
+        assert pw[6] <= PATH_PAIRS
+        why = {n for bit, n in ((1, "bad"), (2, "conflict"), (4, "presence"), (8, "forced")) if pw[1] & bit}
+        out["path"] = dict(fallback=bool(pw[0]), why=why, ends_all=bool(pw[2] & 1), ends_self=bool(pw[2] & 2),
+                           event_cutoff=None if pw[3] < 0 else int(pw[3]), suppressed=int(pw[4]),
+                           commit_cutoff=None if pw[5] < 0 else int(pw[5]), form=form,
+                           pairs=[(int(pw[8 + 4 * k]), int(pw[9 + 4 * k]), int(pw[10 + 4 * k]), int(pw[11 + 4 * k]) & 0xff, bool(pw[11 + 4 * k] >> 8))
+                                  for k in range(pw[6])])
+    return out
 
 
 def obs_env(spec, tile, rows8):

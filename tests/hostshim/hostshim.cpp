@@ -17,12 +17,17 @@ using namespace mgx;
 
 static const JumpTable kJump{};
 
+// the path report of shim_step_env (tests/hostshim/__init__.py: step_env(..., path=True))
+static const int PATH_PAIRS = 64, PATH_WORDS = 8 + 4 * PATH_PAIRS;
+
 extern "C" int shim_step_env(const MgxSpec *sp, uint8_t *tile /* H*W packed cells, updated, NOT overlaid */,
                              uint8_t *tile_overlaid /* out: tile with agent overlay (render input) */,
                              uint64_t *rows /* A, updated */, const int8_t *act, uint64_t *rng /* 4, updated */,
                              int32_t *step_count, uint8_t *aux /* 16, updated */, double *rew /* A out */,
                              uint8_t *terminated /* A out */, uint8_t *truncated, uint8_t *order_out,
-                             int32_t *n_dirty, int force_serial, const uint8_t *hook_order /* A, or NULL */) {
+                             int32_t *n_dirty, int force_serial, const uint8_t *hook_order /* A, or NULL */,
+                             int form /* 0: the prefix commit, 1: the first-agent shortcut */,
+                             int32_t *path /* PATH_WORDS, or NULL: what the decision logic did (layout: below) */) {
     const StepCfg cf = make_cfg(*sp);
     const int A = cf.A, HWB = cf.H * cf.W * cf.cb;          // (cf.cb: 2 = MgxCell, 1 = the compact MgxCell8; include/mgx.h)
     std::vector<uint64_t> rnd(A);
@@ -56,6 +61,38 @@ extern "C" int shim_step_env(const MgxSpec *sp, uint8_t *tile /* H*W packed cell
         if (ev[ai].moved) m_moved |= 1ull << ai;
     }
     const bool fallback = spec_needs_fallback(m_bad, m_conf, m_pres, m_moved) || force_serial;
+    // an EFFECTIVE action: one that would have moved, turned or written
+    auto effective = [&](int ai) {
+        return ev[ai].moved | ev[ai].writes | (ev[ai].go & (row_dir(ev[ai].nrow) != row_dir(rows[ai])));
+    };
+    if (path) {
+        // [0] fallback  [1] why: 1 bad action, 2 cell conflict, 4 presence & moved, 8 forced  [2] events of the order-free
+        // evaluation: 1 ends-all, 2 ends-self  [3] no-fallback branch: the event cutoff rank (-1: none)  [4] ... and how many
+        // agents with an effective action it suppressed  [5] fallback branch: the commit cutoff rank = where the loop starts
+        // (-1: no fallback)  [6] the number of conflicting pairs  [7] form  [8 + 4k ..]: pair k = the writer's action, the
+        // reader's action, the front cell's type, its state | 256 if it is a box that holds something
+        for (int k = 0; k < PATH_WORDS; ++k) path[k] = 0;
+        path[0] = fallback;
+        path[1] = (m_bad != 0) | ((m_conf != 0) << 1) | (((m_pres != 0) & (m_moved != 0)) << 2) | ((force_serial != 0) << 3);
+        for (int ai = 0; ai < A; ++ai)
+            path[2] |= (int)event_ends_all(cf, ev[ai]) | ((int)event_ends_self(cf, ev[ai]) << 1);
+        path[3] = path[5] = -1;
+        path[7] = form;
+        for (int ai = 0; ai < A; ++ai) {                      // the reader
+            if (!((m_conf >> ai) & 1ull)) continue;
+            for (int j = 0; j < A; ++j) {                     // the writer
+                if (j == ai || woff[j] != ev[ai].off) continue;
+                if (path[6] < PATH_PAIRS) {
+                    int32_t *pp = path + 8 + 4 * path[6];
+                    const uint32_t raw = load_cell_raw(cf.cb, tile + ev[ai].off);
+                    const uint32_t cell = cf.cb == 1 ? cell8_unpack(raw) : cell_unpack(raw);
+                    pp[0] = act[j]; pp[1] = act[ai]; pp[2] = (int32_t)(cell & 0xff);
+                    pp[3] = (int32_t)cell_state(cell) | (((cf.cb != 1) && (cell & 0xff) == T_BOX && (raw & 0x48f0u) != 0) << 8);
+                }
+                ++path[6];
+            }
+        }
+    }
     if (!fallback) {
         // lane by lane, as the kernel: who acts (rank <= cutoff), commit, then the events of the agents that acted
         const int cut = (m_ends_all != 0 && A > 1) ? event_cutoff(ord.data(), m_ends_all, A) : A;
@@ -65,7 +102,9 @@ extern "C" int shim_step_env(const MgxSpec *sp, uint8_t *tile /* H*W packed cell
             const int rank = (A > 1) ? draw_rank(rnd.data(), A, ai) : 0;
             acts[ai] = rank <= cut;
             joint_success |= acts[ai] & ev[ai].success;
+            if (path && !acts[ai] && effective(ai)) ++path[4];
         }
+        if (path && cut < A) path[3] = cut;
         const double r = reward_value(sc, cf.max_steps);
         for (int ai = 0; ai < A; ++ai) {
             if (acts[ai]) {
@@ -78,7 +117,22 @@ extern "C" int shim_step_env(const MgxSpec *sp, uint8_t *tile /* H*W packed cell
                 reinterpret_cast<uint8_t *>(rows)[ai * MGX_AGENT_STRIDE + AG_TERM] = 1;
         }
     } else if (force_serial || A == 1) {
+        if (path) path[5] = 0;
         rc = handle_actions(cf, tile, rows, act, ord.data(), rew, sc, dirty, aux, sp->env_kind);
+    } else if (form == 1) {
+        // the kernel's `!PREFIX || A <= 2` branch: only the agent visited first commits early, and only when it has neither an
+        // unknown action nor an event; P1c picks k0 up from bit 7 of ord[0]
+        const int ai = ord[0];
+        const bool first_ok = !(ev[ai].bad | ev[ai].success | ev[ai].failure);
+        if (first_ok) {
+            ord[0] = (uint8_t)(ai | 0x80);
+            if (ev[ai].go) rows[ai] = ev[ai].nrow;
+            if (ev[ai].unstale) aux[4] = 0;
+            if (ev[ai].writes) { store_cell(cf.cb, tile + ev[ai].off, ev[ai].ncell); dirty(ev[ai].off); }
+        }
+        const int k0 = (ord[0] & 0x80) ? 1 : 0;
+        if (path) path[5] = k0;
+        rc = handle_actions(cf, tile, rows, act, ord.data(), rew, sc, dirty, aux, sp->env_kind, k0);
     } else {
         // the kernel's shortened fallback: the agents ranked below the first blocked one commit with the order-free results, the
         // reference's loop starts at that cutoff (mgx_rules.h: prefix_blocked)
@@ -95,6 +149,7 @@ extern "C" int shim_step_env(const MgxSpec *sp, uint8_t *tile /* H*W packed cell
             if (ev[ai].unstale) aux[4] = 0;
             if (ev[ai].writes) { store_cell(cf.cb, tile + ev[ai].off, ev[ai].ncell); dirty(ev[ai].off); }
         }
+        if (path) path[5] = cut;
         rc = handle_actions(cf, tile, rows, act, ord.data(), rew, sc, dirty, aux, sp->env_kind, cut);
     }
     *n_dirty = fallback ? -nd - 1 : nd;          // negative = the sequential loop ran

@@ -14,7 +14,7 @@ import pytest
 from oracle import binding as ob
 
 GOLDEN = [p for p in sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "*.npz")))
-          if not os.path.basename(p).startswith(("layout_", "wrappers_", "custom_", "customsteps_", "randstate_", "resets_"))]
+          if not os.path.basename(p).startswith(("layout_", "wrappers_", "custom_", "customsteps_", "randstate_", "resets_", "conflict_"))]
 
 
 def load(path):
@@ -203,6 +203,14 @@ def test_oracle_replays_reference_random_states(path):
         np.testing.assert_array_equal(agents, z["agents"][t], err_msg=ctx)
         np.testing.assert_array_equal(rng, z["rng"][t], err_msg=ctx)
         np.testing.assert_array_equal(sc, z["step_count0"] + t + 1, err_msg=ctx)
+
+
+@pytest.mark.parametrize("path", __import__("tests.util", fromlist=["CONFLICT_GOLDEN"]).CONFLICT_GOLDEN,
+                         ids=__import__("tests.util", fromlist=["CONFLICT_IDS"]).CONFLICT_IDS)
+def test_oracle_replays_reference_conflicts(path):
+    """The same on the constructed conflict corpus (tests/golden/conflict_*.npz, oracle/gen_golden.py: record_conflicts): the oracle
+    is what the GPU suite compares with where the reference has nothing to record (unknown actions in a contended env)."""
+    test_oracle_replays_reference_random_states(path)
 
 
 def _filled_boxes(z):

@@ -38,9 +38,9 @@ BOXES = "randstate_10x9_a3_v7_boxes"       # filled boxes: refused by compact ce
 
 
 class Fixture:
-    def __init__(self, name):
+    def __init__(self, name, path=None):
         self.name = name
-        self.z, self.d, self.spec = util.load_golden(FIX[name])
+        self.z, self.d, self.spec = util.load_golden(path or FIX[name])
         self.B, self.T = self.z["grid0"].shape[0], self.z["actions"].shape[0]
         self._dev = {}
 

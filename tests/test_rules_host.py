@@ -26,9 +26,14 @@ CASES = [
 ]
 
 
-@pytest.mark.parametrize("force_serial", [False, True], ids=["fastpath", "serial"])
+#: the kernel's two fallback commits (tests/hostshim: step_env's `form`); the forced sequential loop has no form
+FORM_CASES = [("prefix", False), ("first", False), ("prefix", True)]
+FORM_IDS = ["fastpath", "fastpath_first", "serial"]
+
+
+@pytest.mark.parametrize("form,force_serial", FORM_CASES, ids=FORM_IDS)
 @pytest.mark.parametrize("spec", CASES, ids=lambda s: f"{s.width}x{s.height}_a{s.num_agents}_v{s.view_size}")
-def test_rules_match_oracle_on_random_states(spec, force_serial):
+def test_rules_match_oracle_on_random_states(spec, force_serial, form):
     B, T = 24, 12
     st = util.random_state(spec, B, seed=spec.width * 100 + spec.num_agents)
     ref = {k: v.copy() for k, v in st.items()}
@@ -43,7 +48,7 @@ def test_rules_match_oracle_on_random_states(spec, force_serial):
             sd, ref["grid"], ref["agents"], ref["rng"], ref["step_count"], act, ref["target"])
         for b in range(B):
             out = hostshim.step_env(spec, st["grid"][b], st["agents"][b], act[b], st["rng"][b],
-                                    st["step_count"][b], st["target"][b], force_serial)
+                                    st["step_count"][b], st["target"][b], force_serial, form=form)
             n_serial += out["serial"]; n_total += 1
             st["step_count"][b] = out["step_count"]
             ctx = f"step {t} env {b}"
@@ -67,13 +72,13 @@ def test_rules_match_oracle_on_random_states(spec, force_serial):
 COMPACT = [dataclasses.replace(s, cell_bytes=1) for s in (CASES[0], CASES[1], CASES[2], CASES[6], CASES[9])]
 
 
-@pytest.mark.parametrize("force_serial", [False, True], ids=["fastpath", "serial"])
+@pytest.mark.parametrize("form,force_serial", FORM_CASES, ids=FORM_IDS)
 @pytest.mark.parametrize("spec", COMPACT, ids=lambda s: f"{s.width}x{s.height}_a{s.num_agents}_v{s.view_size}_{s.env_kind}")
-def test_rules_on_compact_cells_match_oracle(spec, force_serial):
+def test_rules_on_compact_cells_match_oracle(spec, force_serial, form):
     """The same rules on COMPACT one-byte cells (include/mgx.h: MgxCell8, EnvSpec.cell_bytes = 1: type and state coded jointly):
     the host shim packs the tile that way, the rules read / write it through the format-aware accessors, and every output and the
     whole post-step state must equal the oracle's -- which knows nothing about cell formats."""
-    test_rules_match_oracle_on_random_states(spec, force_serial)
+    test_rules_match_oracle_on_random_states(spec, force_serial, form)
 
 
 def test_compact_cell_codes_round_trip():
@@ -92,7 +97,13 @@ def test_compact_cell_codes_round_trip():
 
 
 @pytest.mark.parametrize("path", util.GOLDEN, ids=util.GOLDEN_IDS)
-def test_rules_replay_goldens(path):
+def test_rules_replay_goldens_first_form(path):
+    """The same replay with the kernel's first-agent shortcut as the fallback commit (tests/hostshim: form="first")."""
+    test_rules_replay_goldens(path, form="first")
+
+
+@pytest.mark.parametrize("path", util.GOLDEN, ids=util.GOLDEN_IDS)
+def test_rules_replay_goldens(path, form="prefix"):
     from multigrid_amd import layouts
     z, d, spec = util.load_golden(path)
     tile = layouts.grid_to_product(z["grid0"]); rows = layouts.pack_agents(z["agents0"])
@@ -100,7 +111,7 @@ def test_rules_replay_goldens(path):
     np.testing.assert_array_equal(hostshim.obs_env(spec, tile, rows), z["obs0"])
     for t in range(z["actions"].shape[0]):
         out = hostshim.step_env(spec, tile, rows, np.ascontiguousarray(z["actions"][t]), rng, sc, target,
-                                hook_order=z["hook_order"][t] if "hook_order" in z.files else None)
+                                hook_order=z["hook_order"][t] if "hook_order" in z.files else None, form=form)
         sc = out["step_count"]
         ctx = f"step {t}"
         np.testing.assert_array_equal(out["order"][:spec.num_agents] if spec.num_agents > 1 else [0],
@@ -155,11 +166,7 @@ def test_pcg64_advance_equals_that_many_numpy_draws():
         assert (int(w[0]), int(w[1]), int(w[2]), int(w[3])) == (st["state"] & m, st["state"] >> 64, st["inc"] & m, st["inc"] >> 64), (seed, k, n)
 
 
-@pytest.mark.parametrize("force_serial", [False, True], ids=["fastpath", "serial"])
-@pytest.mark.parametrize("path", util.RANDSTATE_GOLDEN, ids=util.RANDSTATE_IDS)
-def test_rules_replay_reference_random_states(path, force_serial):
-    """The g++ build of mgx_rules.h, env by env, against the reference's own bytes on the random-state corpus
-    (tests/golden/randstate_*.npz): every output, the post-step grid, agents, generator words and step count, every step."""
+def _replay_reference_states(path, force_serial, form):
     z, d, spec = util.load_golden(path)
     B, T = z["grid0"].shape[0], z["actions"].shape[0]
     assert spec.env_kind in ("empty", "blockedunlockpickup")
@@ -168,8 +175,9 @@ def test_rules_replay_reference_random_states(path, force_serial):
         rng, sc, aux = z["rng0"][b].copy(), int(z["step_count0"][b]), z["aux"][b].copy()
         np.testing.assert_array_equal(hostshim.obs_env(spec, tile, rows), z["obs0"][b])
         for t in range(T):
-            out = hostshim.step_env(spec, tile, rows, np.ascontiguousarray(z["actions"][t, b]), rng, sc, aux, force_serial)
-            ctx = f"env {b} step {t}"
+            out = hostshim.step_env(spec, tile, rows, np.ascontiguousarray(z["actions"][t, b]), rng, sc, aux, force_serial,
+                                    form=form)
+            ctx = f"env {b} step {t}" + (f" ({z['scenario'][b]})" if "scenario" in z.files else "")
             assert out["rc"] == 0, ctx
             sc = out["step_count"]
             assert sc == int(z["step_count0"][b]) + t + 1, ctx
@@ -180,3 +188,19 @@ def test_rules_replay_reference_random_states(path, force_serial):
             np.testing.assert_array_equal(tile, z["grid"][t, b], err_msg=ctx)
             np.testing.assert_array_equal(rows, z["agents"][t, b], err_msg=ctx)
             np.testing.assert_array_equal(rng, z["rng"][t, b], err_msg=ctx)
+
+
+@pytest.mark.parametrize("form,force_serial", FORM_CASES, ids=FORM_IDS)
+@pytest.mark.parametrize("path", util.RANDSTATE_GOLDEN, ids=util.RANDSTATE_IDS)
+def test_rules_replay_reference_random_states(path, force_serial, form):
+    """The g++ build of mgx_rules.h, env by env, against the reference's own bytes on the random-state corpus
+    (tests/golden/randstate_*.npz): every output, the post-step grid, agents, generator words and step count, every step."""
+    _replay_reference_states(path, force_serial, form)
+
+
+@pytest.mark.parametrize("form,force_serial", FORM_CASES, ids=FORM_IDS)
+@pytest.mark.parametrize("path", util.CONFLICT_GOLDEN, ids=util.CONFLICT_IDS)
+def test_rules_replay_reference_conflicts(path, force_serial, form):
+    """The same replay on the constructed conflict corpus (tests/golden/conflict_*.npz, oracle/gen_golden.py: record_conflicts):
+    envs in which the visiting order decides the outcome, in both of the kernel's fallback commits."""
+    _replay_reference_states(path, force_serial, form)

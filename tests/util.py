@@ -15,7 +15,7 @@ from oracle import binding as ob
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 _ALL = sorted(glob.glob(os.path.join(GOLDEN_DIR, "*.npz")))
 #: rollout fixtures (state + actions + per-step outputs) and reset/layout fixtures, both written by oracle/gen_golden.py
-GOLDEN = [p for p in _ALL if not os.path.basename(p).startswith(("layout_", "wrappers_", "custom_", "customsteps_", "randstate_", "resets_"))]
+GOLDEN = [p for p in _ALL if not os.path.basename(p).startswith(("layout_", "wrappers_", "custom_", "customsteps_", "randstate_", "resets_", "conflict_"))]
 GOLDEN_IDS = [os.path.basename(p)[:-4] for p in GOLDEN]
 LAYOUT_GOLDEN = [p for p in _ALL if os.path.basename(p).startswith("layout_")]
 LAYOUT_IDS = [os.path.basename(p)[:-4] for p in LAYOUT_GOLDEN]
@@ -34,6 +34,10 @@ CUSTOM_STEPS_IDS = [os.path.basename(p)[:-4] for p in CUSTOM_STEPS_GOLDEN]
 #: (oracle/gen_golden.py: record_random_states)
 RANDSTATE_GOLDEN = [p for p in _ALL if os.path.basename(p).startswith("randstate_")]
 RANDSTATE_IDS = [os.path.basename(p)[:-4] for p in RANDSTATE_GOLDEN]
+#: constructed envs in which the visiting order decides the outcome, recorded over the reference in the layout of the random-state
+#: corpus (oracle/gen_golden.py: record_conflicts); `scenario` names what each env holds
+CONFLICT_GOLDEN = [p for p in _ALL if os.path.basename(p).startswith("conflict_")]
+CONFLICT_IDS = [os.path.basename(p)[:-4] for p in CONFLICT_GOLDEN]
 #: single resets of the reference from given states of its two generators, one generator configuration per file; `resets_con_*`:
 #: from constructed states whose bounded draws re-sample (oracle/gen_golden.py: record_resets)
 RESETS_GOLDEN = [p for p in _ALL if os.path.basename(p).startswith("resets_") and not os.path.basename(p).startswith("resets_chain_")]
