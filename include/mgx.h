@@ -235,13 +235,16 @@ int mgx_unpack_grid(const MgxCell *packed, int64_t n_cells, uint8_t *cells3, voi
  * kernel; nothing else in this library re-checks what it is handed):
  *   bad i32[4], the caller initialises it to {0, 0, 0, INT32_MAX}:  bad[0] += cells that are not a valid packed cell (reserved
  *   bits, type > 10, color > 5, state > 2, opaque bit inconsistent with (type, state): multigrid/utils/obs.py:46-63),
- *   bad[1] += outer-ring cells that are not WALL, bad[2] += agent rows outside the walls / with direction > 3 / with a carried
- *   cell the format cannot hold (agents may be NULL: not checked), bad[3] = min index of an env with a violation. */
+ *   bad[1] += outer-ring cells that are not WALL, bad[2] += agent rows outside the walls (x or y) / with direction > 3 / with
+ *   terminated > 1 / with colour > 5 / with a carried cell the format cannot hold (its type > 10, colour > 5, state > 2, or a content
+ *   that is not a box's -- on compact cells any content) (agents may be NULL: not checked), bad[3] = min index of an env with a
+ *   violation.  Every count is of CELLS / ROWS: one that breaks several rules counts once. */
 int mgx_pack_grid_env(const uint8_t *cells3, int64_t batch, int32_t height, int32_t width, MgxCell *packed, int32_t *bad,
                       void *stream);
 int mgx_check_grid(const MgxSpec *spec, int64_t batch, const MgxCell *grid, const uint8_t *agents, int32_t *bad, void *stream);
 /* (ABI 9) the same conversions for COMPACT cells (MgxCell8, spec->cell_bytes = 1): bad[0] also counts what only the compact
- * format cannot hold (a state on anything but a door / an agent overlay). */
+ * format cannot hold: a box's content, a state on anything but a door / an agent overlay, a door's state 3 and the types 11..15
+ * (both would read back as one of the joint codes).  bad[0] counts cells: one that breaks several rules counts once. */
 int mgx_pack_grid8_env(const uint8_t *cells3, int64_t batch, int32_t height, int32_t width, MgxCell8 *packed, int32_t *bad,
                        void *stream);
 int mgx_unpack_grid8(const MgxCell8 *packed, int64_t n_cells, uint8_t *cells3, void *stream);
@@ -275,12 +278,16 @@ int mgx_rollout_info(const MgxSpec *spec, int64_t batch, int32_t persistent, Mgx
  * env, multigrid/rllib/__init__.py:110-111) for a flat array of cells:
  *   cells u8[n_cells, 3]  ->  out u8[n_cells, D],  D = dim_sizes[0] + dim_sizes[1] + dim_sizes[2]  (<= 32),
  *   out[c, off_d + cells[c, d]] = 1, off = (0, dim_sizes[0], dim_sizes[0] + dim_sizes[1]); everything else 0.
- * The reference uses dim_sizes = (11, 6, 4) (wrappers.py:139-140).  `out` must be 16-byte aligned. */
+ * A value cells[c, d] >= dim_sizes[d] sets NO channel of field d (the reference's loop would run into the next field, or past the
+ * row); the other fields of that cell are unaffected.
+ * The reference uses dim_sizes = (11, 6, 4) (wrappers.py:139-140).  `out` must be 16-byte aligned (MGX_ERR_INVALID_ARGUMENT
+ * otherwise); `cells` may have any alignment.  D > 32: MGX_ERR_UNSUPPORTED. */
 int mgx_one_hot(const uint8_t *cells, int64_t n_cells, const int32_t *dim_sizes, uint8_t *out, void *stream);
 
 /* Replaces FullyObsWrapper.observation (multigrid/wrappers.py:48-58): out u8[B, W, H, 3] = Grid.state ([x][y], the
  * reference's own orientation) with every agent's (10, color, dir) written at its position in index order,
- * terminated agents included.  One env's cells and output are staged in 64 KiB of LDS: MGX_ERR_UNSUPPORTED when
+ * terminated agents included.  An agent row with x >= W or y >= H writes nothing (no such row occurs in a reachable state: the
+ * image is then the one without that agent).  One env's cells and output are staged in 64 KiB of LDS: MGX_ERR_UNSUPPORTED when
  * (cell_bytes + 3) * W * H + 96 > 65536 (cell_bytes 1 / 2 / 3: squares up to 127 / 114 / 104);
  * BatchedMultiGridEnv.full_obs builds larger grids' tensor from the unpacked grid instead. */
 int mgx_full_obs(const MgxSpec *spec, int64_t batch, const MgxCell *grid, const uint8_t *agents, uint8_t *out,

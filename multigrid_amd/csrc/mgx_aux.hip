@@ -11,6 +11,7 @@
 #include <limits.h>
 #include <stdint.h>
 
+#include "mgx_aux_geom.h"
 #include "mgx_rules.h"
 
 extern "C" void mgx_internal_set_hip_error(int e);      // mgx_kernels.hip: what mgx_last_hip_error() reports
@@ -41,7 +42,7 @@ __device__ __forceinline__ void wave_sync() {          // LDS traffic inside ONE
 // in LDS, (2) each thread assembles 16 output bytes at a time from the masks of the 1-2 cells they span (any D works)
 // and stores them as one vector.
 // ---------------------------------------------------------------------------------------------------------------
-constexpr int kOhCells = 1024;
+// (kOhCells: mgx_aux_geom.h)
 
 __device__ __forceinline__ uint32_t one_hot_mask(uint32_t c, int d0, int d1, int d2) {
     const uint32_t p0 = c & 0xffu, p1 = (c >> 8) & 0xffu, p2 = (c >> 16) & 0xffu;
@@ -292,17 +293,20 @@ __global__ __launch_bounds__(256) void pack_grid_kernel(const uint8_t *__restric
         }
         // the state byte's upper six bits: a box's content (kind | colour << 3, mgx_rules.h), nothing on any other cell
         const uint32_t content = (c >> 18) & 0x3fu;
-        nbad += ((c & 0xf0u) != 0) | (((c >> 8) & 0xf8u) != 0)
-              | ((content != 0) & (((c & 0xffu) != (uint32_t)T_BOX) | ((content & 7u) == 0) | ((content >> 3) > 5u)));
+        // (bad[0] counts CELLS: one that breaks several rules counts once)
+        bool cbad = ((c & 0xf0u) != 0) | (((c >> 8) & 0xf8u) != 0)
+                  | ((content != 0) & (((c & 0xffu) != (uint32_t)T_BOX) | ((content & 7u) == 0) | ((content >> 3) > 5u)));
         if constexpr (C8) {
-            nbad += content != 0;                                        // (the compact format has no room for one)
-            const uint32_t t = c & 0xffu;
-            nbad += (((c >> 16) & 3u) != 0) & (t != (uint32_t)T_DOOR) & (t != (uint32_t)T_AGENT);
-            nbad += (t > 10u) & (t < 16u);                               // (types 11..15 would alias the joint codes)
+            cbad |= content != 0;                                        // (the compact format has no room for one)
+            const uint32_t t = c & 0xffu, st = (c >> 16) & 3u;
+            cbad |= (st != 0) & (t != (uint32_t)T_DOOR) & (t != (uint32_t)T_AGENT);
+            cbad |= (t == (uint32_t)T_DOOR) & (st == 3u);                // (door state 3 would alias the overlay facing 1)
+            cbad |= (t > 10u) & (t < 16u);                               // (types 11..15 would alias the joint codes)
             v[k] = (OutT)cell8_pack(c);
         } else {
             v[k] = (OutT)cell_pack(c);
         }
+        nbad += cbad;
         if (W > 0) {
             const bool ring = (x == 0) | (x == W - 1) | (y == 0) | (y == H - 1);
             nring += (i0 + k < n) & ring & (c != CELL_WALL);
@@ -722,8 +726,7 @@ int mgx_one_hot(const uint8_t *cells, int64_t n_cells, const int32_t *dim_sizes,
     if (D > 32) return MGX_ERR_UNSUPPORTED;
     if (n_cells == 0) return MGX_OK;
     if (!cells || !out || misaligned(out, 16)) return MGX_ERR_INVALID_ARGUMENT;
-    const int64_t chunks = (n_cells + kOhCells - 1) / kOhCells;
-    const int64_t blocks = chunks < 256 * 16 ? chunks : 256 * 16;
+    const int64_t blocks = one_hot_blocks(n_cells);
     const uint32_t inv_D = (uint32_t)(((1ull << 32) + D - 1) / D);
     hipLaunchKernelGGL(one_hot_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), cells,
                        n_cells, d0, d1, d2, inv_D, out);
@@ -738,21 +741,13 @@ int mgx_full_obs(const MgxSpec *spec, int64_t batch, const MgxCell *grid, const 
     const int HW = spec->width * spec->height;
     if (spec->cell_bytes < 0 || spec->cell_bytes > 3) return MGX_ERR_INVALID_ARGUMENT;
     const int cb = spec->cell_bytes == 1 ? 1 : (spec->cell_bytes == 3 ? 3 : kCellBytes);
-    if ((cb + 3) * HW + 2 * 48 > 64 * 1024) return MGX_ERR_UNSUPPORTED;
+    if (!full_obs_fits(spec->width, spec->height, cb)) return MGX_ERR_UNSUPPORTED;
     if (batch == 0) return MGX_OK;
     if (!grid || !agents || !out || misaligned(agents, 8) || misaligned(grid, 16) || misaligned(out, 16))
         return MGX_ERR_INVALID_ARGUMENT;
-    int G = (6 * 1024) / (HW * 3);                                // ~10 KiB of LDS per wavefront
-    if (G < 1) G = 1;
-    if (G * HW > 65535) G = 65535 / HW;
-    while (G > 1 && (batch + G - 1) / G < 4096) G = (G + 1) / 2;  // small batches: spread over the chip
-    const int in_buf = (G * HW * cb + 15 + 16 + 15) & ~15;                 // skew + over-read pad
-    const int out_buf = (G * HW * 3 + 15 + 16 + 15) & ~15;
-    const int wave_lds = in_buf + out_buf;
-    int wpb = 4;
-    while (wpb > 1 && wpb * wave_lds > 64 * 1024) wpb >>= 1;
-    const int64_t nwaves = (batch + G - 1) / G;
-    const int64_t blocks = (nwaves + wpb - 1) / wpb;
+    const FullObsGeom geo = full_obs_geom(spec->width, spec->height, cb, batch);      // (mgx_aux_geom.h)
+    const int G = geo.G, in_buf = geo.in_buf, wave_lds = geo.wave_lds, wpb = geo.wpb;
+    const int64_t blocks = geo.blocks;
     if (blocks > INT_MAX) return MGX_ERR_UNSUPPORTED;
     const uint32_t inv_W = (uint32_t)(((1ull << 32) + spec->width - 1) / spec->width);
     const uint32_t inv_H = (uint32_t)(((1ull << 32) + spec->height - 1) / spec->height);
@@ -862,9 +857,8 @@ int mgx_reset_done(const MgxSpec *spec, int64_t batch, int64_t first_env, int32_
     const int64_t blocks = (batch + 255) / 256;
     if (blocks > INT_MAX) return MGX_ERR_UNSUPPORTED;
     // widest copy unit that divides the layout size and the base addresses
-    int unit = 16;
-    while (unit > 1 && (HW3 % unit || misaligned(grid, unit) || misaligned(pool_grid, unit))) unit >>= 1;
-    const int units = HW3 / unit;
+    const ResetUnit ru = reset_copy_unit(HW3, reinterpret_cast<uintptr_t>(grid), reinterpret_cast<uintptr_t>(pool_grid));   // (mgx_aux_geom.h)
+    const int unit = ru.unit, units = ru.units;
     const uint32_t inv_units = (uint32_t)(((1ull << 32) + units - 1) / units);
     const uint32_t inv_A = (uint32_t)(((1ull << 32) + spec->num_agents - 1) / spec->num_agents);
     hipStream_t st = static_cast<hipStream_t>(stream);

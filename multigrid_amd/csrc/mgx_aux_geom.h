@@ -1,0 +1,65 @@
+// mgx_aux_geom.h -- the host-side launch arithmetic of the streaming kernels in mgx_aux.hip, in one place and without any HIP
+// dependency: the launchers call these functions, and tests/hostshim exports them so that tests/test_aux_branch_census.py derives
+// which kernel paths a shape reaches from the SAME arithmetic (not from a Python copy of it).
+#ifndef MGX_AUX_GEOM_H
+#define MGX_AUX_GEOM_H
+
+#include <stdint.h>
+
+namespace mgx {
+
+// one_hot: a workgroup takes chunks of kOhCells cells; at most 4096 workgroups, the rest by a grid-stride loop
+constexpr int kOhCells = 1024;
+constexpr int kOhMaxBlocks = 256 * 16;
+
+inline int64_t one_hot_chunks(int64_t n_cells) { return (n_cells + kOhCells - 1) / kOhCells; }
+inline int64_t one_hot_blocks(int64_t n_cells) {
+    const int64_t chunks = one_hot_chunks(n_cells);
+    return chunks < kOhMaxBlocks ? chunks : kOhMaxBlocks;
+}
+
+// full_obs: G consecutive envs per wavefront, each wavefront with its own two LDS buffers
+struct FullObsGeom {
+    int G;                  // envs per wavefront
+    int in_buf, out_buf;    // LDS bytes of a wavefront's input / output staging (skew + over-read pad included)
+    int wave_lds;           // in_buf + out_buf
+    int wpb;                // wavefronts per workgroup
+    int64_t nwaves, blocks;
+};
+
+// does one env fit the 64 KiB of LDS?  (cb: bytes per grid cell, 1 / 2 / 3)
+inline bool full_obs_fits(int W, int H, int cb) { return (cb + 3) * W * H + 2 * 48 <= 64 * 1024; }
+
+inline FullObsGeom full_obs_geom(int W, int H, int cb, int64_t batch) {
+    FullObsGeom g;
+    const int HW = W * H;
+    g.G = (6 * 1024) / (HW * 3);                                      // ~10 KiB of LDS per wavefront
+    if (g.G < 1) g.G = 1;
+    if (g.G * HW > 65535) g.G = 65535 / HW;
+    while (g.G > 1 && (batch + g.G - 1) / g.G < 4096) g.G = (g.G + 1) / 2;   // small batches: spread over the chip
+    g.in_buf = (g.G * HW * cb + 15 + 16 + 15) & ~15;                  // skew + over-read pad
+    g.out_buf = (g.G * HW * 3 + 15 + 16 + 15) & ~15;
+    g.wave_lds = g.in_buf + g.out_buf;
+    g.wpb = 4;
+    while (g.wpb > 1 && g.wpb * g.wave_lds > 64 * 1024) g.wpb >>= 1;
+    g.nwaves = (batch + g.G - 1) / g.G;
+    g.blocks = (g.nwaves + g.wpb - 1) / g.wpb;
+    return g;
+}
+
+// reset_done: the widest copy unit (16, 8, 4, 2 or 1 bytes) that divides an env's grid bytes and both base addresses
+struct ResetUnit {
+    int unit, units;        // bytes per copy, copies per env
+};
+
+inline ResetUnit reset_copy_unit(int env_bytes, uintptr_t grid, uintptr_t pool_grid) {
+    ResetUnit r;
+    r.unit = 16;
+    while (r.unit > 1 && (env_bytes % r.unit || (grid & (uintptr_t)(r.unit - 1)) || (pool_grid & (uintptr_t)(r.unit - 1)))) r.unit >>= 1;
+    r.units = env_bytes / r.unit;
+    return r;
+}
+
+}  // namespace mgx
+
+#endif

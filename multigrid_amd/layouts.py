@@ -140,6 +140,8 @@ def pack_cells8(grid_hwc: np.ndarray) -> np.ndarray:
                          "needs the 16-bit cells)")
     if ((s != 0) & (t != int(Type.door)) & (t != int(Type.agent))).any():
         raise ValueError("the compact cell format holds a state only on doors and agent overlays")
+    if ((t == int(Type.door)) & (s > 2)).any():
+        raise ValueError("the compact cell format holds a door's states 0..2 (a fourth would read back as an agent overlay)")
     tc = np.where(s == 0, t, np.where(t == int(Type.door), 10 + s, 12 + s))
     opaque = (t == int(Type.wall)) | ((t == int(Type.door)) & (s != 0))
     return (tc | (c << 4) | (opaque.astype(np.uint16) << 7)).astype(np.uint8)

@@ -9,6 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(HERE, "libmgx_hostshim.so")
 SRC = os.path.join(HERE, "hostshim.cpp")
 RULES = os.path.join(os.path.dirname(os.path.dirname(HERE)), "multigrid_amd", "csrc", "mgx_rules.h")
+GEOM = os.path.join(os.path.dirname(RULES), "mgx_aux_geom.h")
 
 _lib = None
 
@@ -22,7 +23,7 @@ def lib():
                                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", out, SRC])
             _lib = C.CDLL(out)
             return _lib
-        if not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(SRC), os.path.getmtime(RULES)):
+        if not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(SRC), os.path.getmtime(RULES), os.path.getmtime(GEOM)):
             subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wall",
                                    "-o", LIB, SRC])
         _lib = C.CDLL(LIB)
@@ -97,3 +98,25 @@ def obs_env(spec, tile, rows8):
     obs = np.empty((A, v, v, 3), np.uint8)
     assert lib().shim_obs_env(C.byref(sc), _p(over, C.c_uint8), _p(rows, C.c_uint64), _p(obs, C.c_uint8)) == 0
     return obs
+
+
+def full_obs_geom(W, H, cb, batch):
+    """mgx_full_obs' launch geometry (csrc/mgx_aux_geom.h), or None where the launcher answers UNSUPPORTED."""
+    out = np.zeros(7, np.int64)
+    if not lib().shim_full_obs_geom(int(W), int(H), int(cb), C.c_int64(int(batch)), _p(out, C.c_int64)):
+        return None
+    return dict(zip(("G", "in_buf", "out_buf", "wave_lds", "wpb", "nwaves", "blocks"), (int(v) for v in out)))
+
+
+def reset_unit(env_bytes, grid_addr=0, pool_addr=0):
+    """mgx_reset_done's copy unit for a layout of `env_bytes` at these base addresses: (unit bytes, units per env)."""
+    out = np.zeros(2, np.int32)
+    lib().shim_reset_unit(int(env_bytes), C.c_uint64(int(grid_addr)), C.c_uint64(int(pool_addr)), _p(out, C.c_int32))
+    return int(out[0]), int(out[1])
+
+
+def one_hot_geom(n_cells):
+    """mgx_one_hot's launch: (cells per chunk, chunks, workgroups)."""
+    out = np.zeros(3, np.int64)
+    lib().shim_one_hot_geom(C.c_int64(int(n_cells)), _p(out, C.c_int64))
+    return tuple(int(v) for v in out)

@@ -11,6 +11,7 @@
 #include <cstring>
 #include <vector>
 
+#include "../../multigrid_amd/csrc/mgx_aux_geom.h"
 #include "../../multigrid_amd/csrc/mgx_rules.h"
 
 using namespace mgx;
@@ -244,4 +245,25 @@ extern "C" int shim_pool_index(int64_t first_env, int64_t b, int32_t ep, int32_t
 extern "C" void shim_pcg64_advance(uint64_t *state4, int k, uint32_t n) {
     const uint64_t unit[4] = {kJump.w[k][0], kJump.w[k][1], kJump.w[k][2], kJump.w[k][3]};
     pcg64_advance(state4[0], state4[1], state4[2], state4[3], unit, n);
+}
+
+// the launch arithmetic of the streaming kernels (mgx_aux_geom.h: what mgx_full_obs / mgx_reset_done / mgx_one_hot launch with),
+// for tests/test_aux_branch_census.py.  out[7] = G, in_buf, out_buf, wave_lds, waves per workgroup, wavefronts, workgroups;
+// returns 0 when an env does not fit the LDS staging (mgx_full_obs: MGX_ERR_UNSUPPORTED)
+extern "C" int shim_full_obs_geom(int W, int H, int cb, int64_t batch, int64_t *out) {
+    if (!full_obs_fits(W, H, cb)) return 0;
+    const FullObsGeom g = full_obs_geom(W, H, cb, batch);
+    out[0] = g.G; out[1] = g.in_buf; out[2] = g.out_buf; out[3] = g.wave_lds; out[4] = g.wpb; out[5] = g.nwaves; out[6] = g.blocks;
+    return 1;
+}
+
+// out[2] = the copy unit in bytes, copies per env
+extern "C" void shim_reset_unit(int env_bytes, uint64_t grid_addr, uint64_t pool_addr, int32_t *out) {
+    const ResetUnit r = reset_copy_unit(env_bytes, (uintptr_t)grid_addr, (uintptr_t)pool_addr);
+    out[0] = r.unit; out[1] = r.units;
+}
+
+// out[3] = cells per chunk, chunks, workgroups
+extern "C" void shim_one_hot_geom(int64_t n_cells, int64_t *out) {
+    out[0] = kOhCells; out[1] = one_hot_chunks(n_cells); out[2] = one_hot_blocks(n_cells);
 }
