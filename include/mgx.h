@@ -426,6 +426,31 @@ typedef struct MgxLayoutGen {
 int mgx_reset_generate(const MgxSpec *spec, int64_t batch, const MgxLayoutGen *gen, MgxCell *grid, uint8_t *agents,
                        uint64_t *rng, int32_t *step_count, uint8_t *aux, int32_t *episode, uint8_t *was_reset, void *stream);
 
+/* Restart the envs the CALLER chooses (additive to ABI 11): what the reference's caller does with `env.reset(seed=s)` on any env
+ * it likes, finished or not (multigrid/base.py:250-301).  mgx_reset_select is mgx_reset_done, mgx_reset_generate_select is
+ * mgx_reset_generate, with the done test replaced by `select`:
+ *   a chosen env      restarts exactly as the done-based call restarts a finished one (pool: layout = (first_env + b + episode[b] *
+ *                     7919) mod K); step_count[b] = 0; episode[b] += 1; was_reset[b] = 1
+ *   any other env     keeps every byte of its state -- a finished env that is not chosen stays finished; was_reset[b] = 0
+ * rng_words != NULL re-seeds env.np_random of the chosen envs with the restart (reset(seed=...), base.py:269): the generation draws
+ * from a fresh generator with these PCG64 words and no pending 32-bit half (gen_state[b][5] is not read), and `rng[b]` /
+ * gen_state[b][5] come out as the generation left that generator; the pool form stores rng[b] = rng_words[b].  The placement stream
+ * gen_state[b][0..4] is never re-seeded: it is the construction-time generator, which reset(seed) does not replace.
+ * Limits and return codes are those of mgx_reset_done / mgx_reset_generate; rng_words 8-byte aligned; batch == 0 is a no-op.  `pool`
+ * carries first_env, the layout pool, `episode` and `was_reset` (may be NULL).  The staging slots of MgxGenStage need no attention:
+ * episode[b] += 1 makes every slot and pending snapshot of a chosen env stale (tag != episode). */
+typedef struct MgxResetSelect {
+    const uint8_t  *select;     /* u8[B]: non-zero = restart this env; NULL = every env */
+    const uint64_t *rng_words;  /* u64[B,4]: PCG64 words installed as env.np_random of the selected envs
+                                   (fresh generator, empty 32-bit buffer); NULL = the stream is left running */
+} MgxResetSelect;
+
+int mgx_reset_select(const MgxSpec *spec, int64_t batch, const MgxResetSelect *sel, const MgxAutoReset *pool, MgxCell *grid,
+                     uint8_t *agents, uint64_t *rng, int32_t *step_count, uint8_t *aux, void *stream);
+int mgx_reset_generate_select(const MgxSpec *spec, int64_t batch, const MgxResetSelect *sel, const MgxLayoutGen *gen, MgxCell *grid,
+                              uint8_t *agents, uint64_t *rng, int32_t *step_count, uint8_t *aux, int32_t *episode,
+                              uint8_t *was_reset, void *stream);
+
 /* (ABI 8) The staging slots' generator as a launch of its own: serves every pending snapshot request of `gen->stage` (one lane
  * per env; envs without a request cost one load).  Enqueue it on a stream BESIDE the one the steps run on, ordered behind the step
  * that took the snapshots (an event): with gen->stage.external = 1 and a lead of a few steps the next episodes of the envs about to

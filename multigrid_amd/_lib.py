@@ -28,7 +28,7 @@ EXPORTS = ("mgx_abi_version", "mgx_error_string", "mgx_last_hip_error", "mgx_gen
            "mgx_step_ex", "mgx_step_chains", "mgx_sub_shards",
            "mgx_pack_grid_env", "mgx_check_grid", "mgx_pack_grid8_env", "mgx_unpack_grid8", "mgx_shape_key", "mgx_shape_register", "mgx_stage_generate",
            "mgx_persistent_waves", "mgx_step_persistent", "mgx_persistent_post", "mgx_persistent_wait", "mgx_persistent_feed",
-           "mgx_rollout_info", "mgx_render_atlas", "mgx_render")
+           "mgx_rollout_info", "mgx_render_atlas", "mgx_render", "mgx_reset_select", "mgx_reset_generate_select")
 
 
 class MgxLaunchInfo(C.Structure):
@@ -46,6 +46,11 @@ class MgxAutoReset(C.Structure):
     """include/mgx.h: struct MgxAutoReset."""
     _fields_ = [("first_env", C.c_int64), ("pool_size", C.c_int32), ("pool_grid", C.c_void_p),
                 ("pool_agents", C.c_void_p), ("pool_aux", C.c_void_p), ("episode", C.c_void_p), ("was_reset", C.c_void_p)]
+
+
+class MgxResetSelect(C.Structure):
+    """include/mgx.h: struct MgxResetSelect (the envs a selected restart takes, and their new np_random words)."""
+    _fields_ = [("select", C.c_void_p), ("rng_words", C.c_void_p)]
 
 
 class MgxGenStage(C.Structure):
@@ -128,6 +133,10 @@ def lib() -> C.CDLL:
     L.mgx_reset_done.argtypes = [C.POINTER(MgxSpecC), i64, i64, C.c_int32] + [vp] * 10
     L.mgx_reset_generate.restype = C.c_int
     L.mgx_reset_generate.argtypes = [C.POINTER(MgxSpecC), i64, C.POINTER(MgxLayoutGen)] + [vp] * 8
+    L.mgx_reset_select.restype = C.c_int
+    L.mgx_reset_select.argtypes = [C.POINTER(MgxSpecC), i64, C.POINTER(MgxResetSelect), C.POINTER(MgxAutoReset)] + [vp] * 6
+    L.mgx_reset_generate_select.restype = C.c_int
+    L.mgx_reset_generate_select.argtypes = [C.POINTER(MgxSpecC), i64, C.POINTER(MgxResetSelect), C.POINTER(MgxLayoutGen)] + [vp] * 8
     L.mgx_stage_generate.restype = C.c_int
     L.mgx_stage_generate.argtypes = [C.POINTER(MgxSpecC), i64, C.POINTER(MgxLayoutGen), vp, vp, vp]
     L.mgx_step_generate.restype = C.c_int

@@ -218,6 +218,7 @@ class BatchedMultiGridEnv:
             setattr(self, name, self._out[offs[name]:offs[name] + nbytes].view(dt).view(shape))
         self.err.copy_(torch.tensor([0, INT32_MAX], dtype=torch.int32))
         self._loaded = False
+        self._seeded = False             # np_random holds generator words (seed / seed_synthetic / load_state(rng=) / reset(seed))
         self._act_shape = torch.Size((B, A))
         self._bound = {}                 # (auto_reset, one_hot, generate[, parts]) -> pre-bound step launcher (ops.HipBackend)
         self._layout_version = 0         # bumped whenever the layout pool / generator tensors are REPLACED: sub-shards and
@@ -288,6 +289,7 @@ class BatchedMultiGridEnv:
             if r.dtype == np.uint64:
                 r = r.view(np.int64)
             self.rng.copy_(prep(r, (B, 4), torch.int64))
+            self._seeded = True
         if aux is None and target is not None:                 # BlockedUnlockPickup convenience: (type, color, state[, 0])
             t = np.zeros(np.asarray(target).shape[:-1] + (16,), dtype=np.uint8)
             t[..., :min(4, np.asarray(target).shape[-1])] = np.asarray(target)[..., :4]
@@ -324,6 +326,7 @@ class BatchedMultiGridEnv:
         self.join()
         idx = self.first_env + np.arange(self.batch)
         self.rng.copy_(torch.from_numpy(rnglib.words_from_seed_and_index(seed, idx).view(np.int64)))
+        self._seeded = True
         self._state_written()
 
     def seed_synthetic(self, seed: int):
@@ -332,6 +335,7 @@ class BatchedMultiGridEnv:
         self.join()
         words = rnglib.synthetic_words(self.batch, seed, self.first_env)
         self.rng.copy_(torch.from_numpy(words.view(np.int64)))
+        self._seeded = True
         self._state_written()
 
     def _reset_err(self):
@@ -558,6 +562,7 @@ class BatchedMultiGridEnv:
             c._loaded, c._act_shape, c._bound = True, torch.Size((hi - lo, self.spec.num_agents)), {}
             c._parent, c._made_version, c._layout_version = self, self._layout_version, 0
             c._chain_streams, c._chains_pending, c._chains_P, c._session = [], False, 1, None
+            c._seeded = self._seeded
             c._one_hot = self._one_hot[lo:hi] if getattr(self, "_one_hot", None) is not None else None
             c._pool = getattr(self, "_pool", None)
             c._gen = None
@@ -915,6 +920,57 @@ class BatchedMultiGridEnv:
         self.backend.reset_done(self.batch, self.first_env, self._pool, self.cells, self.agents, self.step_count,
                                 self.aux, self.episode, self.was_reset)
         return self.was_reset
+
+    def reset(self, seed: int | None = None, mask: torch.Tensor | None = None, one_hot: bool = False):
+        """`obs, info = env.reset(seed=seed)` of the reference (multigrid/base.py:250-301) for the envs the caller chooses, on the
+        device: they start a new episode from the layout generator (`set_layout_generator`: the reference's own `_gen_grid`, draw
+        for draw) or the layout pool (`set_layout_pool`), whether their episode is over or not.  Also the way to a FIRST episode:
+        with nothing loaded yet, `reset()` of the whole batch is the initial state.
+
+        seed     None: every np_random stream runs on, as an unseeded reset() leaves it (no host work at all).  An int: np_random of
+                 the chosen envs is re-seeded with the restart by the rule `seed()` documents -- global env g gets
+                 Generator(PCG64(SeedSequence([seed, g]))), global env 0 SeedSequence(seed) -- and the generation draws from that
+                 fresh generator (the words are made on the host: one [B,4] copy to the device; only chosen envs take them).  The
+                 placement generators of `set_layout_generator(layout_seed=...)` are never re-seeded: the reference's are made at
+                 construction time, and its reset(seed) leaves them alone.
+        mask     bool / uint8 [B] on the env's device: the envs to restart (None = all).  Read by the kernel as it is: no copy, no
+                 host synchronisation.  Envs outside it keep every byte of their state -- a finished env stays finished.
+        Returns `gen_obs(one_hot)` of the whole batch; `was_reset` holds the selection; reward / terminated / truncated are not
+        touched.  The staging slots of a staged generator need no attention: a restart advances the env's episode counter, which
+        is what makes a slot or a pending snapshot stale (include/mgx.h: MgxGenStage, tag != episode)."""
+        self._no_session("reset")
+        gen, pool = getattr(self, "_gen", None), getattr(self, "_pool", None)
+        if gen is None and pool is None:
+            raise RuntimeError("call set_layout_pool() or set_layout_generator() first")
+        sel = None
+        if mask is not None:
+            self._need_state()
+            if not torch.is_tensor(mask) or mask.dtype not in (torch.bool, torch.uint8) or tuple(mask.shape) != (self.batch,) \
+                    or mask.device != self.cells.device or not mask.is_contiguous():
+                raise ValueError(f"mask must be a contiguous bool or uint8 tensor of shape ({self.batch},) on {self.cells.device}")
+            sel = mask.view(torch.uint8) if mask.dtype is torch.bool else mask
+        if seed is None and not self._loaded and not self._seeded:
+            raise ValueError("reset(): np_random has never been seeded (all-zero PCG64 words are not a generator): pass seed=, or "
+                             "call seed() / seed_synthetic() first")
+        self.join()
+        words = None
+        if seed is not None:
+            idx = self.first_env + np.arange(self.batch)
+            words = torch.from_numpy(rnglib.words_from_seed_and_index(int(seed), idx).view(np.int64)).to(self.device)
+        aux = self.aux if self.spec.env_kind != "empty" else None
+        if gen is not None:
+            side = (gen.get("stage") or {}).get("stream")
+            if side is not None:                 # (generator launches beside the steps read gen_state / rng: behind them)
+                torch.cuda.current_stream(self.device).wait_stream(side)
+            self.backend.reset_generate_select(self.batch, gen, sel, words, self.cells, self.agents, self.rng, self.step_count,
+                                               aux, self.episode, self.was_reset)
+        else:
+            self.backend.reset_select(self.batch, self.first_env, pool, sel, words, self.cells, self.agents, self.rng,
+                                      self.step_count, self.aux, self.episode, self.was_reset)
+        if seed is not None:
+            self._seeded = True
+        self._loaded = True
+        return self.gen_obs(one_hot)
 
     def outputs_to_host(self) -> dict:
         """Everything the last step / gen_obs handed back, on the host after ONE device-to-host copy (into a pinned buffer) and one

@@ -499,6 +499,56 @@ __global__ __launch_bounds__(256) void reset_done_kernel(int HWB, int A, int max
             reinterpret_cast<uint4 *>(aux)[e0 + l_env[j]] = reinterpret_cast<const uint4 *>(pool_aux)[l_lay[j]];
 }
 
+// reset_select (include/mgx.h: mgx_reset_select): reset_done's scheme for the envs the CALLER chose -- one byte per env (`select ==
+// NULL`: every env) instead of the done test, so a wavefront nobody was chosen in ends after one byte load per lane.  An env that is
+// not chosen keeps everything, finished or not; only its was_reset byte is cleared.  `rng_words`: a chosen env's np_random becomes
+// the fresh generator reset(seed=...) installs (base.py:269).
+template <typename VecT>
+__global__ __launch_bounds__(256) void reset_select_kernel(int HWB, int A, int64_t batch, int64_t first_env, int K,
+                                                           uint32_t inv_units, uint32_t inv_A,
+                                                           const uint8_t *__restrict__ select,
+                                                           const uint64_t *__restrict__ rng_words,
+                                                           const uint8_t *__restrict__ pool_grid,
+                                                           const uint8_t *__restrict__ pool_agents,
+                                                           const uint8_t *__restrict__ pool_aux, uint8_t *grid,
+                                                           uint8_t *agents, uint64_t *rng, int32_t *step_count, uint8_t *aux,
+                                                           int32_t *episode, uint8_t *was_reset) {
+    __shared__ int s_env[4][64], s_lay[4][64];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t e0 = ((int64_t)blockIdx.x * 4 + wave) * 64;
+    if (e0 >= batch) return;
+    const int64_t b = e0 + lane;
+    bool sel = false;
+    int layout = 0;
+    if (b < batch) {
+        sel = select == nullptr || select[b] != 0;
+        if (sel) {
+            const int ep = episode[b];
+            layout = (int)((uint64_t)(first_env + b + (int64_t)ep * 7919) % (uint64_t)K);       // (reset_done's walk of the pool)
+            episode[b] = ep + 1;
+            step_count[b] = 0;
+            if (rng_words)
+                for (int k = 0; k < 4; ++k) rng[b * 4 + k] = rng_words[b * 4 + k];
+        }
+        if (was_reset) was_reset[b] = (uint8_t)sel;
+    }
+    const uint64_t mask = __builtin_amdgcn_ballot_w64(sel);
+    if (mask == 0) return;
+    const int n = __builtin_popcountll(mask);
+    if (sel) {
+        const int pos = __builtin_popcountll(mask & ((1ull << lane) - 1ull));
+        s_env[wave][pos] = lane; s_lay[wave][pos] = layout;
+    }
+    wave_sync();
+    const int *l_env = s_env[wave], *l_lay = s_lay[wave];
+    copy_layouts<VecT>(n, HWB / (int)sizeof(VecT), inv_units, e0, HWB, l_env, l_lay, pool_grid, grid, lane);
+    copy_layouts<uint64_t>(n, A, inv_A, e0, (int64_t)A * MGX_AGENT_STRIDE, l_env, l_lay, pool_agents, agents, lane);   // 8-byte rows
+    if (aux && pool_aux)
+        for (int j = lane; j < n; j += 64)
+            reinterpret_cast<uint4 *>(aux)[e0 + l_env[j]] = reinterpret_cast<const uint4 *>(pool_aux)[l_lay[j]];
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Persistent stepping, the producer's side (include/mgx.h: MgxPersistent; the consumer is MODE 3 of the fused kernel).
 // A granule = {tag << 32 | 4 action bytes}, written by ONE relaxed agent-scope 8-byte store (write-through): the data is the
@@ -866,6 +916,42 @@ int mgx_reset_done(const MgxSpec *spec, int64_t batch, int64_t first_env, int32_
     hipLaunchKernelGGL(reset_done_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, HW3, spec->num_agents,           \
                        spec->max_steps, batch, first_env, pool_size, inv_units, inv_A, pool_grid, pool_agents, pool_aux, grid, \
                        agents, step_count, aux, episode, was_reset)
+    switch (unit) {
+    case 16: MGX_RESET(uint4); break;
+    case 8:  MGX_RESET(uint64_t); break;
+    case 4:  MGX_RESET(uint32_t); break;
+    case 2:  MGX_RESET(uint16_t); break;
+    default: MGX_RESET(uint8_t); break;
+    }
+#undef MGX_RESET
+    return finish_launch();
+}
+
+int mgx_reset_select(const MgxSpec *spec, int64_t batch, const MgxResetSelect *sel, const MgxAutoReset *pool, MgxCell *grid_c,
+                     uint8_t *agents, uint64_t *rng, int32_t *step_count, uint8_t *aux, void *stream) {
+    if (!spec || !sel || !pool || batch < 0 || pool->pool_size < 1 || pool->first_env < 0) return MGX_ERR_INVALID_ARGUMENT;
+    if (batch == 0) return MGX_OK;
+    const uint8_t *pool_grid = reinterpret_cast<const uint8_t *>(pool->pool_grid);
+    uint8_t *grid = reinterpret_cast<uint8_t *>(grid_c);
+    if (!pool_grid || !pool->pool_agents || !grid || !agents || !step_count || !pool->episode || (sel->rng_words && !rng))
+        return MGX_ERR_INVALID_ARGUMENT;
+    if (misaligned(agents, 8) || misaligned(pool->pool_agents, 8) || misaligned(aux, 16) || misaligned(pool->pool_aux, 16)
+        || misaligned(rng, 8) || misaligned(sel->rng_words, 8) || misaligned(step_count, 4) || misaligned(pool->episode, 4)
+        || ((spec->cell_bytes == 0 || spec->cell_bytes == 2) && (misaligned(grid, 2) || misaligned(pool_grid, 2))))
+        return MGX_ERR_INVALID_ARGUMENT;
+    if (spec->cell_bytes < 0 || spec->cell_bytes > 3) return MGX_ERR_INVALID_ARGUMENT;
+    const int HW3 = spec->width * spec->height * (spec->cell_bytes == 1 ? 1 : (spec->cell_bytes == 3 ? 3 : kCellBytes));   // bytes of one env's grid
+    const int64_t blocks = (batch + 255) / 256;
+    if (blocks > INT_MAX) return MGX_ERR_UNSUPPORTED;
+    const ResetUnit ru = reset_copy_unit(HW3, reinterpret_cast<uintptr_t>(grid), reinterpret_cast<uintptr_t>(pool_grid));   // (mgx_aux_geom.h)
+    const int unit = ru.unit, units = ru.units;
+    const uint32_t inv_units = (uint32_t)(((1ull << 32) + units - 1) / units);
+    const uint32_t inv_A = (uint32_t)(((1ull << 32) + spec->num_agents - 1) / spec->num_agents);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+#define MGX_RESET(T)                                                                                                   \
+    hipLaunchKernelGGL(reset_select_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, HW3, spec->num_agents, batch,  \
+                       pool->first_env, pool->pool_size, inv_units, inv_A, sel->select, sel->rng_words, pool_grid,      \
+                       pool->pool_agents, pool->pool_aux, grid, agents, rng, step_count, aux, pool->episode, pool->was_reset)
     switch (unit) {
     case 16: MGX_RESET(uint4); break;
     case 8:  MGX_RESET(uint64_t); break;

@@ -135,6 +135,51 @@ __global__ __launch_bounds__(64) void stage_candidates_kernel(const GenArgs a) {
     st.tag[b * 4 + k] = a.episode[b];
 }
 
+// mgx_reset_generate_select (include/mgx.h): reset_generate_kernel with the done test replaced by the caller's choice -- one byte
+// per env (`select == NULL`: every env), so a wavefront nobody was chosen in ends after one byte load per lane.  An env that is not
+// chosen is left exactly as it is, finished or not; only its was_reset byte is cleared.  `rng_words`: the chosen env's np_random
+// becomes a FRESH generator for this generation (reset(seed=...), base.py:269): its PCG64 words, no pending 32-bit half.  The
+// placement stream gen_state[0..4] is the construction-time generator, which reset(seed) does not replace.
+struct GenSelectArgs {
+    GenArgs g;
+    const uint8_t *select;
+    const uint64_t *rng_words;
+};
+
+__global__ __launch_bounds__(64) void reset_generate_select_kernel(const GenSelectArgs s) {
+    extern __shared__ uint8_t lds[];
+    const GenArgs &a = s.g;
+    const int lane = threadIdx.x;
+    const int W = a.sp.width, H = a.sp.height, A = a.sp.num_agents, HWB = H * W * kCellBytes;
+    const int64_t e0 = (int64_t)blockIdx.x * 64;
+    const int64_t b = e0 + lane;
+    bool sel = false;
+    if (b < a.batch) {
+        sel = s.select == nullptr || s.select[b] != 0;
+        if (a.was_reset) a.was_reset[b] = (uint8_t)sel;
+    }
+    const uint64_t mask = __builtin_amdgcn_ballot_w64(sel);
+    if (mask == 0) return;
+    copy_blank(a.gen, a.grid, e0, HWB, mask, lane);                                  // (1) all lanes
+    // (2) overwrites cells that OTHER lanes of this wavefront have just stored: their stores must have left the wave first
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_s_waitcnt(0x0F70);                                              // vmcnt(0)
+    __builtin_amdgcn_wave_barrier();
+    if (!sel) return;
+    NpGen lay, npr;                                                                  // (2) the owning lane
+    uint64_t *gs = a.gen.gen_state + b * 6;
+    const uint64_t *nw = s.rng_words ? s.rng_words + b * 4 : a.rng + b * 4;
+    for (int k = 0; k < 4; ++k) { lay.s[k] = gs[k]; npr.s[k] = nw[k]; }
+    lay.buf = gs[4]; npr.buf = s.rng_words ? 0 : gs[5];                              // (a fresh generator has no pending half)
+    const uint4 aux = generate_episode(a.gen, W, H, A, lay, npr, lds + lane * (2 * A), a.grid + b * HWB,
+                                       reinterpret_cast<uint64_t *>(a.agents) + b * A);
+    if (a.aux) reinterpret_cast<uint4 *>(a.aux)[b] = aux;
+    for (int k = 0; k < 4; ++k) { gs[k] = lay.s[k]; a.rng[b * 4 + k] = npr.s[k]; }
+    gs[4] = lay.buf; gs[5] = npr.buf;
+    a.step_count[b] = 0;                                                             // base.py:292
+    a.episode[b] += 1;
+}
+
 inline bool misaligned(const void *p, uintptr_t al) { return (reinterpret_cast<uintptr_t>(p) & (al - 1)) != 0; }
 
 }  // namespace
@@ -182,6 +227,33 @@ int mgx_reset_generate(const MgxSpec *spec, int64_t batch, const MgxLayoutGen *g
     if (blocks > INT_MAX) return MGX_ERR_UNSUPPORTED;
     GenArgs ga{*spec, batch, *gen, reinterpret_cast<uint8_t *>(grid), agents, rng, step_count, aux, episode, was_reset};
     hipLaunchKernelGGL(reset_generate_kernel, dim3((unsigned)blocks), dim3(64), (size_t)(64 * 2 * spec->num_agents),
+                       static_cast<hipStream_t>(stream), ga);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { mgx_internal_set_hip_error((int)e); return MGX_ERR_LAUNCH; }
+    return MGX_OK;
+}
+
+int mgx_reset_generate_select(const MgxSpec *spec, int64_t batch, const MgxResetSelect *sel, const MgxLayoutGen *gen, MgxCell *grid,
+                              uint8_t *agents, uint64_t *rng, int32_t *step_count, uint8_t *aux, int32_t *episode,
+                              uint8_t *was_reset, void *stream) {
+    if (!spec || !sel || !gen || batch < 0) return MGX_ERR_INVALID_ARGUMENT;
+    if (spec->width < 3 || spec->height < 3 || spec->num_agents < 1 || spec->num_agents > MGX_MAX_AGENTS)
+        return MGX_ERR_INVALID_ARGUMENT;
+    if (spec->width > 254 || spec->height > 254) return MGX_ERR_UNSUPPORTED;         // positions are bytes, 0xff = off the grid
+    if (spec->cell_bytes == 1) return MGX_ERR_UNSUPPORTED;                           // (generation writes 16-bit cells)
+    if (batch == 0) return MGX_OK;
+    if (!gen->blank || !gen->gen_state || !grid || !agents || !rng || !step_count || !episode) return MGX_ERR_INVALID_ARGUMENT;
+    if (misaligned(agents, 8) || misaligned(rng, 8) || misaligned(gen->gen_state, 8) || misaligned(aux, 16)
+        || misaligned(step_count, 4) || misaligned(episode, 4) || misaligned(sel->rng_words, 8))
+        return MGX_ERR_INVALID_ARGUMENT;
+    const int rc = check_layout_gen(spec, gen);
+    if (rc) return rc;
+    if (spec->env_kind != MGX_KIND_EMPTY && !aux) return MGX_ERR_INVALID_ARGUMENT;
+    const int64_t blocks = (batch + 63) / 64;
+    if (blocks > INT_MAX) return MGX_ERR_UNSUPPORTED;
+    GenSelectArgs ga{{*spec, batch, *gen, reinterpret_cast<uint8_t *>(grid), agents, rng, step_count, aux, episode, was_reset},
+                     sel->select, sel->rng_words};
+    hipLaunchKernelGGL(reset_generate_select_kernel, dim3((unsigned)blocks), dim3(64), (size_t)(64 * 2 * spec->num_agents),
                        static_cast<hipStream_t>(stream), ga);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { mgx_internal_set_hip_error((int)e); return MGX_ERR_LAUNCH; }

@@ -443,5 +443,26 @@ class HipBackend:
                 was_reset.data_ptr() if was_reset is not None else None, _stream(grid.device))
         _lib.check(rc, "mgx_reset_generate")
 
+    def reset_select(self, B, first_env, pool, select, rng_words, grid, agents, rng, step_count, target, episode, was_reset):
+        """mgx_reset_select: the envs of `select` (u8 / bool [B], None = all) restart from the layout pool; `rng_words` (i64[B,4] or
+        None) re-seeds their np_random.  No torch op: one launch on torch's current stream, nothing synchronises."""
+        ar = self._auto_reset_struct((first_env, pool, episode, was_reset))
+        sel = _lib.MgxResetSelect(_ptr(select), _ptr(rng_words))
+        with torch.cuda.device(grid.device):
+            rc = _lib.lib().mgx_reset_select(
+                C.byref(self.sc), B, C.byref(sel), C.byref(ar), grid.data_ptr(), agents.data_ptr(), rng.data_ptr(),
+                step_count.data_ptr(), target.data_ptr() if pool[2] is not None else None, _stream(grid.device))
+        _lib.check(rc, "mgx_reset_select")
+
+    def reset_generate_select(self, B, gen, select, rng_words, grid, agents, rng, step_count, aux, episode, was_reset):
+        """mgx_reset_generate_select: the envs of `select` are regenerated on the device (`gen` as in `reset_generate`)."""
+        g = self._layout_gen_struct(gen)
+        sel = _lib.MgxResetSelect(_ptr(select), _ptr(rng_words))
+        with torch.cuda.device(grid.device):
+            rc = _lib.lib().mgx_reset_generate_select(
+                C.byref(self.sc), B, C.byref(sel), C.byref(g), grid.data_ptr(), agents.data_ptr(), rng.data_ptr(),
+                step_count.data_ptr(), _ptr(aux), episode.data_ptr(), _ptr(was_reset), _stream(grid.device))
+        _lib.check(rc, "mgx_reset_generate_select")
+
     def launch_info(self, B) -> dict:
         return _lib.launch_info(self.spec, B)

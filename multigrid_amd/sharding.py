@@ -90,6 +90,17 @@ class NodeEnv:
         for sh in self.shards:
             sh.set_layout_pool(grids, agents, auxs)
 
+    def set_layout_generator(self, kind: str, layout_seed: int = 0, **kw):
+        for sh in self.shards:
+            sh.set_layout_generator(kind, layout_seed, **kw)
+
+    def reset(self, seed=None, mask=None, one_hot: bool = False) -> list:
+        """`BatchedMultiGridEnv.reset` of every shard.  `mask`: bool / uint8 over the GLOBAL batch (or the per-shard list `scatter`
+        makes), cut per shard; the seeds follow the global env index, so the shards' states are those of one env over the whole
+        batch.  Returns the shards' (obs, dir) tuples, as `step()` does."""
+        parts = [None] * len(self.shards) if mask is None else mask if isinstance(mask, (list, tuple)) else self.scatter(mask)
+        return [sh.reset(seed=seed, mask=m, one_hot=one_hot) for sh, m in zip(self.shards, parts)]
+
     def scatter(self, x) -> list:
         """A tensor over the global batch (dimension 0, or dimension 1 of a [T, B, ...] action script when `x.dim() >= 3`) -> its
         per-shard pieces on the shards' devices."""
