@@ -298,7 +298,9 @@ int mgx_full_obs(const MgxSpec *spec, int64_t batch, const MgxCell *grid, const 
  * step_count >= max_steps -- is re-initialised from a pool of K pre-generated layouts
  * (pool_grid u16[K,H,W] packed cells, pool_agents u8[K,A,8], pool_aux u8[K,16] or NULL):
  *   layout = (first_env + b + episode[b] * 7919) mod K;  step_count[b] = 0;  episode[b] += 1;  was_reset[b] = 1.
- * The env's PCG64 stream is left running, as an unseeded reset() does for Empty envs.  `was_reset` may be NULL. */
+ * The env's PCG64 stream is left running, as an unseeded reset() does for Empty envs.  `was_reset` may be NULL.
+ * Checked by the validator mgx_reset_select shares: `step_count` and `episode` must be 4-byte aligned (MGX_ERR_INVALID_ARGUMENT
+ * otherwise, as mgx_reset_select and mgx_reset_generate answer). */
 int mgx_reset_done(const MgxSpec *spec, int64_t batch, int64_t first_env, int32_t pool_size, const MgxCell *pool_grid,
                    const uint8_t *pool_agents, const uint8_t *pool_aux, MgxCell *grid, uint8_t *agents,
                    int32_t *step_count, uint8_t *aux, int32_t *episode, uint8_t *was_reset, void *stream);
@@ -616,7 +618,9 @@ typedef struct MgxPersistent {
 int mgx_persistent_waves(const MgxSpec *spec, int64_t batch, const MgxStepArgs *args, int32_t *waves);
 int mgx_step_persistent(const MgxSpec *spec, int64_t batch, const MgxStepArgs *args, const MgxPersistent *p, void *stream);
 /* actions i8[B,A] (as mgx_step takes them) -> the granules of step `step` (counted from 1); stream-ordered behind whatever
- * produced `actions` on `stream`. */
+ * produced `actions` on `stream`.  This call and mgx_persistent_feed find a granule's env by a 32-bit reciprocal multiply:
+ * MGX_ERR_UNSUPPORTED from B * ceil(A/4) = 2^31 granules on, and already from 2^30 at 17..20 agents and from 1 431 655 766 at 25..28
+ * (5 and 7 granules per env), where that quotient stops being exact. */
 int mgx_persistent_post(const MgxSpec *spec, int64_t batch, const int8_t *actions, uint32_t step, uint64_t *action_granules,
                         void *stream);
 /* Returns (in stream order) once done[w] >= step for every w < waves, or after timeout_ms (then ctrl[1] += 1). */

@@ -3,18 +3,19 @@
 //   mgx_one_hot     OneHotObsWrapper.one_hot        multigrid/wrappers.py:158-190   (HBM write-bound: 3 B in, 21 B out)
 //   mgx_full_obs    FullyObsWrapper.observation     multigrid/wrappers.py:48-58     (grid transpose-copy + agent overlay)
 //   mgx_reset_done  vector-env auto-reset from a pool of pre-generated layouts (build-defined; the reference has no
-//                   batching: its user calls reset() when is_done(), multigrid/base.py:250-301, 534-539)
+//                   batching: its user calls reset() when is_done(), multigrid/base.py:250-301, 534-539); mgx_reset_select is
+//                   the same restart (restart_from_pool, check_reset_pool) for the envs the caller chose: another trigger
 //
-// All three are streaming kernels: 16-byte loads and stores, the byte shuffling in between goes through LDS.
+// All three are streaming kernels: 16-byte loads and stores, the byte shuffling in between goes through LDS.  A division by
+// a launch constant is __umulhi by recip32() of it (mgx_aux_geom.h, with the range it is exact over).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <limits.h>
 #include <stdint.h>
 
 #include "mgx_aux_geom.h"
+#include "mgx_host.h"
 #include "mgx_rules.h"
-
-extern "C" void mgx_internal_set_hip_error(int e);      // mgx_kernels.hip: what mgx_last_hip_error() reports
 
 namespace {
 
@@ -56,7 +57,7 @@ __device__ __forceinline__ uint32_t one_hot_mask(uint32_t c, int d0, int d1, int
 __global__ __launch_bounds__(256) void one_hot_kernel(const uint8_t *__restrict__ x, int64_t n_cells, int d0, int d1, int d2,
                                                       uint32_t inv_D, uint8_t *__restrict__ out) {
     __shared__ __align__(16) uint32_t masks[kOhCells + 32];
-    const int D = d0 + d1 + d2;                                   // 3 <= D <= 32;  inv_D = ceil(2^32 / D)
+    const int D = d0 + d1 + d2;                                   // 3 <= D <= 32;  inv_D = recip32(D)
     const int64_t nchunks = (n_cells + kOhCells - 1) / kOhCells;
     const bool aligned = (reinterpret_cast<uintptr_t>(x) & 3) == 0;
     for (int64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
@@ -84,7 +85,7 @@ __global__ __launch_bounds__(256) void one_hot_kernel(const uint8_t *__restrict_
         const int total = ncell * D;                              // output bytes of this chunk
         uint8_t *dst = out + c_base * D;                          // 16-byte aligned: c_base is a multiple of 1024
         for (int o = threadIdx.x * 16; o < total; o += 256 * 16) {
-            const int cq = (int)__umulhi((uint32_t)o, inv_D);     // o / D, exact for o < 2^20
+            const int cq = (int)__umulhi((uint32_t)o, inv_D);     // o / D, o < 2^20 (mgx_aux_geom.h: recip32)
             const int k0 = o - cq * D;
             uint32_t bits = masks[cq] >> k0;                      // bits of up to 16 consecutive output bytes
             int have = D - k0, c = cq + 1;
@@ -164,7 +165,7 @@ __global__ __launch_bounds__(256) void full_obs_kernel(int W, int H, int A, int 
         int e, r, y, xx;
         if (pow2) { e = i >> shHW; r = i & (HW - 1); y = r >> shW; xx = r & (W - 1); }
         else {
-            e = (int)__umulhi((uint32_t)i, inv_HW);                                         // i / HW  (i < 2^16)
+            e = (int)__umulhi((uint32_t)i, inv_HW);                                         // i / HW, i < 2^16 (mgx_aux_geom.h: recip32)
             r = i - e * HW;
             y = (int)__umulhi((uint32_t)r, inv_W); xx = r - y * W;                          // r / W
         }
@@ -425,10 +426,11 @@ __global__ __launch_bounds__(256) void unpack_grid8_kernel(const uint8_t *__rest
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// reset_done: every env whose episode is over (all agents terminated, or step_count >= max_steps: base.py:534-539)
-// is re-initialised from layout pool[(global_env + episode * stride) mod K]; step_count := 0, episode += 1.
-// One lane per env decides; the wavefront then copies the layouts of its finished envs with all 64 lanes, in the widest
-// unit the layout size allows.
+// reset_done / reset_select: every env whose episode is over (all agents terminated, or step_count >= max_steps:
+// base.py:534-539) -- BY_SELECT: that the caller chose, one `select` byte per env, NULL = every env -- is re-initialised from
+// layout pool[(global_env + episode * stride) mod K]; step_count := 0, episode += 1; `rng_words` (BY_SELECT only): its
+// np_random becomes the fresh generator reset(seed=...) installs (base.py:269).  One lane per env decides; the wavefront then
+// copies the layouts of its restarting envs with all 64 lanes, in the widest unit the layout size allows.
 // ---------------------------------------------------------------------------------------------------------------
 template <typename VecT>
 __device__ __forceinline__ void copy_layouts(int n, int units, uint32_t inv_units, int64_t e0, int64_t env_bytes,
@@ -443,7 +445,7 @@ __device__ __forceinline__ void copy_layouts(int n, int units, uint32_t inv_unit
     } else {                                                      // small layouts: (env, vector) pairs flattened over the lanes
         const int total = n * units;
         for (int k = lane; k < total; k += 64) {
-            // k / units, k < 4096 (units == 1 -- one agent: ceil(2^32 / 1) does not fit the 32-bit reciprocal, which arrived as 0 and
+            // k / units, k < 4096 (mgx_aux_geom.h: recip32; units == 1 -- one agent -- has no 32-bit reciprocal: it arrived as 0 and
             // sent every finished env's row to the first one: found by tests/test_instantiations.py, round 6)
             const int j = units == 1 ? k : (int)__umulhi((uint32_t)k, inv_units), v = k - j * units;
             const VecT *s = reinterpret_cast<const VecT *>(pool + (int64_t)l_lay[j] * env_bytes);
@@ -453,40 +455,46 @@ __device__ __forceinline__ void copy_layouts(int n, int units, uint32_t inv_unit
     }
 }
 
-template <typename VecT>
-__global__ __launch_bounds__(256) void reset_done_kernel(int HWB, int A, int max_steps, int64_t batch, int64_t first_env,
-                                                         int K, uint32_t inv_units, uint32_t inv_A,
-                                                         const uint8_t *__restrict__ pool_grid,
-                                                         const uint8_t *__restrict__ pool_agents,
-                                                         const uint8_t *__restrict__ pool_aux, uint8_t *grid,
-                                                         uint8_t *agents, int32_t *step_count, uint8_t *aux,
-                                                         int32_t *episode, uint8_t *was_reset) {
+template <typename VecT, bool BY_SELECT>
+__device__ __forceinline__ void restart_from_pool(const uint8_t *select, const uint64_t *rng_words, uint64_t *rng, int max_steps, int HWB,
+                                                  int A, int64_t batch, int64_t first_env, int K, uint32_t inv_units, uint32_t inv_A,
+                                                  const uint8_t *pool_grid, const uint8_t *pool_agents, const uint8_t *pool_aux,
+                                                  uint8_t *grid, uint8_t *agents, int32_t *step_count, uint8_t *aux, int32_t *episode,
+                                                  uint8_t *was_reset) {
     __shared__ int s_env[4][64], s_lay[4][64];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t e0 = ((int64_t)blockIdx.x * 4 + wave) * 64;
     if (e0 >= batch) return;
     const int64_t b = e0 + lane;
-    bool done = false;
+    bool go = false;
     int layout = 0;
     if (b < batch) {
-        const uint64_t *rows = reinterpret_cast<const uint64_t *>(agents) + b * A;
-        bool all_term = true;
-        for (int a = 0; a < A; ++a) all_term &= row_term(rows[a]);
-        done = all_term || step_count[b] >= max_steps;
-        if (done) {
+        if constexpr (BY_SELECT) {
+            go = select == nullptr || select[b] != 0;
+        } else {
+            const uint64_t *rows = reinterpret_cast<const uint64_t *>(agents) + b * A;
+            bool all_term = true;
+            for (int a = 0; a < A; ++a) all_term &= row_term(rows[a]);
+            go = all_term || step_count[b] >= max_steps;
+        }
+        if (go) {
             const int ep = episode[b];
             // a fixed odd stride walks the whole pool before repeating; depends only on the GLOBAL env index
             layout = (int)((uint64_t)(first_env + b + (int64_t)ep * 7919) % (uint64_t)K);
             episode[b] = ep + 1;
             step_count[b] = 0;
+            if constexpr (BY_SELECT) {        // (compiled out of reset_done: a NULL that folds away only later moves that kernel's stores)
+                if (rng_words)
+                    for (int k = 0; k < 4; ++k) rng[b * 4 + k] = rng_words[b * 4 + k];
+            }
         }
-        if (was_reset) was_reset[b] = (uint8_t)done;
+        if (was_reset) was_reset[b] = (uint8_t)go;
     }
-    const uint64_t mask = __builtin_amdgcn_ballot_w64(done);
+    const uint64_t mask = __builtin_amdgcn_ballot_w64(go);
     if (mask == 0) return;
     const int n = __builtin_popcountll(mask);
-    if (done) {
+    if (go) {
         const int pos = __builtin_popcountll(mask & ((1ull << lane) - 1ull));
         s_env[wave][pos] = lane; s_lay[wave][pos] = layout;
     }
@@ -499,54 +507,27 @@ __global__ __launch_bounds__(256) void reset_done_kernel(int HWB, int A, int max
             reinterpret_cast<uint4 *>(aux)[e0 + l_env[j]] = reinterpret_cast<const uint4 *>(pool_aux)[l_lay[j]];
 }
 
-// reset_select (include/mgx.h: mgx_reset_select): reset_done's scheme for the envs the CALLER chose -- one byte per env (`select ==
-// NULL`: every env) instead of the done test, so a wavefront nobody was chosen in ends after one byte load per lane.  An env that is
-// not chosen keeps everything, finished or not; only its was_reset byte is cleared.  `rng_words`: a chosen env's np_random becomes
-// the fresh generator reset(seed=...) installs (base.py:269).
 template <typename VecT>
-__global__ __launch_bounds__(256) void reset_select_kernel(int HWB, int A, int64_t batch, int64_t first_env, int K,
-                                                           uint32_t inv_units, uint32_t inv_A,
-                                                           const uint8_t *__restrict__ select,
-                                                           const uint64_t *__restrict__ rng_words,
-                                                           const uint8_t *__restrict__ pool_grid,
-                                                           const uint8_t *__restrict__ pool_agents,
-                                                           const uint8_t *__restrict__ pool_aux, uint8_t *grid,
-                                                           uint8_t *agents, uint64_t *rng, int32_t *step_count, uint8_t *aux,
-                                                           int32_t *episode, uint8_t *was_reset) {
-    __shared__ int s_env[4][64], s_lay[4][64];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t e0 = ((int64_t)blockIdx.x * 4 + wave) * 64;
-    if (e0 >= batch) return;
-    const int64_t b = e0 + lane;
-    bool sel = false;
-    int layout = 0;
-    if (b < batch) {
-        sel = select == nullptr || select[b] != 0;
-        if (sel) {
-            const int ep = episode[b];
-            layout = (int)((uint64_t)(first_env + b + (int64_t)ep * 7919) % (uint64_t)K);       // (reset_done's walk of the pool)
-            episode[b] = ep + 1;
-            step_count[b] = 0;
-            if (rng_words)
-                for (int k = 0; k < 4; ++k) rng[b * 4 + k] = rng_words[b * 4 + k];
-        }
-        if (was_reset) was_reset[b] = (uint8_t)sel;
-    }
-    const uint64_t mask = __builtin_amdgcn_ballot_w64(sel);
-    if (mask == 0) return;
-    const int n = __builtin_popcountll(mask);
-    if (sel) {
-        const int pos = __builtin_popcountll(mask & ((1ull << lane) - 1ull));
-        s_env[wave][pos] = lane; s_lay[wave][pos] = layout;
-    }
-    wave_sync();
-    const int *l_env = s_env[wave], *l_lay = s_lay[wave];
-    copy_layouts<VecT>(n, HWB / (int)sizeof(VecT), inv_units, e0, HWB, l_env, l_lay, pool_grid, grid, lane);
-    copy_layouts<uint64_t>(n, A, inv_A, e0, (int64_t)A * MGX_AGENT_STRIDE, l_env, l_lay, pool_agents, agents, lane);   // 8-byte rows
-    if (aux && pool_aux)
-        for (int j = lane; j < n; j += 64)
-            reinterpret_cast<uint4 *>(aux)[e0 + l_env[j]] = reinterpret_cast<const uint4 *>(pool_aux)[l_lay[j]];
+__global__ __launch_bounds__(256) void reset_done_kernel(int HWB, int A, int max_steps, int64_t batch, int64_t first_env, int K,
+                                                         uint32_t inv_units, uint32_t inv_A, const uint8_t *__restrict__ pool_grid,
+                                                         const uint8_t *__restrict__ pool_agents, const uint8_t *__restrict__ pool_aux,
+                                                         uint8_t *grid, uint8_t *agents, int32_t *step_count, uint8_t *aux,
+                                                         int32_t *episode, uint8_t *was_reset) {
+    restart_from_pool<VecT, false>(nullptr, nullptr, nullptr, max_steps, HWB, A, batch, first_env, K, inv_units, inv_A, pool_grid,
+                                   pool_agents, pool_aux, grid, agents, step_count, aux, episode, was_reset);
+}
+
+// reset_select (include/mgx.h: mgx_reset_select): the envs the CALLER chose, so a wavefront nobody was chosen in ends after one byte
+// load per lane.  An env that is not chosen keeps everything, finished or not; only its was_reset byte is cleared.
+template <typename VecT>
+__global__ __launch_bounds__(256) void reset_select_kernel(int HWB, int A, int64_t batch, int64_t first_env, int K, uint32_t inv_units,
+                                                           uint32_t inv_A, const uint8_t *__restrict__ select,
+                                                           const uint64_t *__restrict__ rng_words, const uint8_t *__restrict__ pool_grid,
+                                                           const uint8_t *__restrict__ pool_agents, const uint8_t *__restrict__ pool_aux,
+                                                           uint8_t *grid, uint8_t *agents, uint64_t *rng, int32_t *step_count,
+                                                           uint8_t *aux, int32_t *episode, uint8_t *was_reset) {
+    restart_from_pool<VecT, true>(select, rng_words, rng, 0, HWB, A, batch, first_env, K, inv_units, inv_A, pool_grid, pool_agents,
+                                  pool_aux, grid, agents, step_count, aux, episode, was_reset);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -573,7 +554,7 @@ __global__ __launch_bounds__(256) void persistent_post_kernel(const int8_t *__re
                                                               uint32_t inv_gpe, uint32_t tag, uint64_t *granules) {
     const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (g >= n_granules) return;
-    const int64_t b = gpe == 1 ? g : (int64_t)(((uint64_t)g * inv_gpe) >> 32);     // g / gpe (n_granules < 2^31: checked by the host)
+    const int64_t b = gpe == 1 ? g : (int64_t)(((uint64_t)g * inv_gpe) >> 32);     // g / gpe (mgx_aux_geom.h: granule_geometry keeps n_granules exact)
     const int q = (int)(g - b * gpe);
     __hip_atomic_store(granules + g, make_granule(actions + b * A, A, q, tag), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -709,26 +690,41 @@ __global__ __launch_bounds__(kFeedThreads) void persistent_feed_kernel(const int
     if (trace && threadIdx.x == 0) trace[2 * T] = __builtin_amdgcn_s_memrealtime();
 }
 
-int finish_launch() {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { mgx_internal_set_hip_error((int)e); return MGX_ERR_LAUNCH; }
+// a restart kernel's instantiation for a copy unit of 16 / 8 / 4 / 2 / 1 bytes (mgx_aux_geom.h: reset_copy_unit)
+#define MGX_BY_UNIT(kernel, unit) \
+    ((unit) == 16 ? kernel<uint4> : (unit) == 8 ? kernel<uint64_t> : (unit) == 4 ? kernel<uint32_t> : (unit) == 2 ? kernel<uint16_t> : kernel<uint8_t>)
+
+// What mgx_reset_done and mgx_reset_select check alike, and the launch both make of it (MGX_OK at batch > 0: `pl` is filled in).
+struct PoolLaunch {
+    int HWB, unit;                    // bytes of one env's grid, bytes per copy
+    uint32_t inv_units, inv_A;        // recip32 of the copies per env / of the agents (copy_layouts)
+    dim3 blocks;
+};
+
+int check_reset_pool(const MgxSpec *spec, int64_t batch, const MgxAutoReset &pool, const MgxCell *grid, const uint8_t *agents,
+                     const uint64_t *rng, const uint64_t *rng_words, const int32_t *step_count, const uint8_t *aux, PoolLaunch &pl) {
+    if (!spec || batch < 0 || pool.pool_size < 1 || pool.first_env < 0) return MGX_ERR_INVALID_ARGUMENT;
+    if (batch == 0) return MGX_OK;
+    if (!pool.pool_grid || !pool.pool_agents || !grid || !agents || !step_count || !pool.episode || (rng_words && !rng))
+        return MGX_ERR_INVALID_ARGUMENT;
+    if (misaligned(agents, 8) || misaligned(pool.pool_agents, 8) || misaligned(aux, 16) || misaligned(pool.pool_aux, 16)
+        || misaligned(rng, 8) || misaligned(rng_words, 8) || misaligned(step_count, 4) || misaligned(pool.episode, 4)
+        || ((spec->cell_bytes == 0 || spec->cell_bytes == 2) && (misaligned(grid, 2) || misaligned(pool.pool_grid, 2))))
+        return MGX_ERR_INVALID_ARGUMENT;
+    if (spec->cell_bytes < 0 || spec->cell_bytes > 3) return MGX_ERR_INVALID_ARGUMENT;
+    pl.HWB = spec->width * spec->height * (spec->cell_bytes == 1 ? 1 : (spec->cell_bytes == 3 ? 3 : kCellBytes));
+    const int64_t blocks = (batch + 255) / 256;
+    if (blocks > INT_MAX) return MGX_ERR_UNSUPPORTED;
+    pl.blocks = dim3((unsigned)blocks);
+    // widest copy unit that divides the layout size and the base addresses (mgx_aux_geom.h)
+    const ResetUnit ru = reset_copy_unit(pl.HWB, reinterpret_cast<uintptr_t>(grid), reinterpret_cast<uintptr_t>(pool.pool_grid));
+    pl.unit = ru.unit; pl.inv_units = recip32((uint32_t)ru.units); pl.inv_A = recip32((uint32_t)spec->num_agents);
     return MGX_OK;
 }
-
-inline bool misaligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
 
 }  // namespace
 
 extern "C" {
-
-static int granule_geometry(const MgxSpec *spec, int64_t batch, int &gpe, uint32_t &inv_gpe, int64_t &ng) {
-    if (!spec || batch < 1 || spec->num_agents < 1 || spec->num_agents > MGX_MAX_AGENTS) return MGX_ERR_INVALID_ARGUMENT;
-    gpe = (spec->num_agents + 3) / 4;
-    ng = batch * gpe;
-    if (ng >= ((int64_t)1 << 31)) return MGX_ERR_UNSUPPORTED;
-    inv_gpe = (uint32_t)((((uint64_t)1 << 32) + gpe - 1) / gpe);           // ceil(2^32 / gpe): g / gpe exact for g < 2^31, gpe <= 8
-    return MGX_OK;
-}
 
 int mgx_persistent_post(const MgxSpec *spec, int64_t batch, const int8_t *actions, uint32_t step, uint64_t *action_granules,
                         void *stream) {
@@ -777,7 +773,7 @@ int mgx_one_hot(const uint8_t *cells, int64_t n_cells, const int32_t *dim_sizes,
     if (n_cells == 0) return MGX_OK;
     if (!cells || !out || misaligned(out, 16)) return MGX_ERR_INVALID_ARGUMENT;
     const int64_t blocks = one_hot_blocks(n_cells);
-    const uint32_t inv_D = (uint32_t)(((1ull << 32) + D - 1) / D);
+    const uint32_t inv_D = recip32((uint32_t)D);
     hipLaunchKernelGGL(one_hot_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), cells,
                        n_cells, d0, d1, d2, inv_D, out);
     return finish_launch();
@@ -799,10 +795,7 @@ int mgx_full_obs(const MgxSpec *spec, int64_t batch, const MgxCell *grid, const 
     const int G = geo.G, in_buf = geo.in_buf, wave_lds = geo.wave_lds, wpb = geo.wpb;
     const int64_t blocks = geo.blocks;
     if (blocks > INT_MAX) return MGX_ERR_UNSUPPORTED;
-    const uint32_t inv_W = (uint32_t)(((1ull << 32) + spec->width - 1) / spec->width);
-    const uint32_t inv_H = (uint32_t)(((1ull << 32) + spec->height - 1) / spec->height);
-    const uint32_t hw = (uint32_t)HW;
-    const uint32_t inv_HW = (uint32_t)(((1ull << 32) + hw - 1) / hw);
+    const uint32_t inv_W = recip32((uint32_t)spec->width), inv_H = recip32((uint32_t)spec->height), inv_HW = recip32((uint32_t)HW);
     auto *kern = cb == 1 ? full_obs_kernel<1> : cb == 3 ? full_obs_kernel<3> : full_obs_kernel<2>;
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * wpb), (size_t)(wpb * wave_lds),
                        static_cast<hipStream_t>(stream), spec->width, spec->height, spec->num_agents, G, wave_lds, in_buf, inv_W,
@@ -891,75 +884,30 @@ int mgx_unpack_grid(const MgxCell *packed, int64_t n_cells, uint8_t *cells3, voi
     return finish_launch();
 }
 
-int mgx_reset_done(const MgxSpec *spec, int64_t batch, int64_t first_env, int32_t pool_size, const MgxCell *pool_grid_c,
-                   const uint8_t *pool_agents, const uint8_t *pool_aux, MgxCell *grid_c, uint8_t *agents,
+int mgx_reset_done(const MgxSpec *spec, int64_t batch, int64_t first_env, int32_t pool_size, const MgxCell *pool_grid,
+                   const uint8_t *pool_agents, const uint8_t *pool_aux, MgxCell *grid, uint8_t *agents,
                    int32_t *step_count, uint8_t *aux, int32_t *episode, uint8_t *was_reset, void *stream) {
-    if (!spec || batch < 0 || pool_size < 1 || first_env < 0) return MGX_ERR_INVALID_ARGUMENT;
-    if (batch == 0) return MGX_OK;
-    const uint8_t *pool_grid = reinterpret_cast<const uint8_t *>(pool_grid_c);
-    uint8_t *grid = reinterpret_cast<uint8_t *>(grid_c);
-    if (!pool_grid || !pool_agents || !grid || !agents || !step_count || !episode) return MGX_ERR_INVALID_ARGUMENT;
-    if (misaligned(agents, 8) || misaligned(pool_agents, 8) || misaligned(aux, 16) || misaligned(pool_aux, 16)
-        || ((spec->cell_bytes == 0 || spec->cell_bytes == 2) && (misaligned(grid, 2) || misaligned(pool_grid, 2))))
-        return MGX_ERR_INVALID_ARGUMENT;
-    if (spec->cell_bytes < 0 || spec->cell_bytes > 3) return MGX_ERR_INVALID_ARGUMENT;
-    const int HW3 = spec->width * spec->height * (spec->cell_bytes == 1 ? 1 : (spec->cell_bytes == 3 ? 3 : kCellBytes));   // bytes of one env's grid
-    const int64_t blocks = (batch + 255) / 256;
-    if (blocks > INT_MAX) return MGX_ERR_UNSUPPORTED;
-    // widest copy unit that divides the layout size and the base addresses
-    const ResetUnit ru = reset_copy_unit(HW3, reinterpret_cast<uintptr_t>(grid), reinterpret_cast<uintptr_t>(pool_grid));   // (mgx_aux_geom.h)
-    const int unit = ru.unit, units = ru.units;
-    const uint32_t inv_units = (uint32_t)(((1ull << 32) + units - 1) / units);
-    const uint32_t inv_A = (uint32_t)(((1ull << 32) + spec->num_agents - 1) / spec->num_agents);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-#define MGX_RESET(T)                                                                                                   \
-    hipLaunchKernelGGL(reset_done_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, HW3, spec->num_agents,           \
-                       spec->max_steps, batch, first_env, pool_size, inv_units, inv_A, pool_grid, pool_agents, pool_aux, grid, \
-                       agents, step_count, aux, episode, was_reset)
-    switch (unit) {
-    case 16: MGX_RESET(uint4); break;
-    case 8:  MGX_RESET(uint64_t); break;
-    case 4:  MGX_RESET(uint32_t); break;
-    case 2:  MGX_RESET(uint16_t); break;
-    default: MGX_RESET(uint8_t); break;
-    }
-#undef MGX_RESET
+    const MgxAutoReset pool{first_env, pool_size, pool_grid, pool_agents, pool_aux, episode, was_reset};
+    PoolLaunch pl;
+    const int rc = check_reset_pool(spec, batch, pool, grid, agents, nullptr, nullptr, step_count, aux, pl);
+    if (rc || batch == 0) return rc;
+    hipLaunchKernelGGL(MGX_BY_UNIT(reset_done_kernel, pl.unit), pl.blocks, dim3(256), 0, static_cast<hipStream_t>(stream), pl.HWB,
+                       spec->num_agents, spec->max_steps, batch, first_env, pool_size, pl.inv_units, pl.inv_A,
+                       reinterpret_cast<const uint8_t *>(pool_grid), pool_agents, pool_aux, reinterpret_cast<uint8_t *>(grid), agents,
+                       step_count, aux, episode, was_reset);
     return finish_launch();
 }
 
-int mgx_reset_select(const MgxSpec *spec, int64_t batch, const MgxResetSelect *sel, const MgxAutoReset *pool, MgxCell *grid_c,
+int mgx_reset_select(const MgxSpec *spec, int64_t batch, const MgxResetSelect *sel, const MgxAutoReset *pool, MgxCell *grid,
                      uint8_t *agents, uint64_t *rng, int32_t *step_count, uint8_t *aux, void *stream) {
-    if (!spec || !sel || !pool || batch < 0 || pool->pool_size < 1 || pool->first_env < 0) return MGX_ERR_INVALID_ARGUMENT;
-    if (batch == 0) return MGX_OK;
-    const uint8_t *pool_grid = reinterpret_cast<const uint8_t *>(pool->pool_grid);
-    uint8_t *grid = reinterpret_cast<uint8_t *>(grid_c);
-    if (!pool_grid || !pool->pool_agents || !grid || !agents || !step_count || !pool->episode || (sel->rng_words && !rng))
-        return MGX_ERR_INVALID_ARGUMENT;
-    if (misaligned(agents, 8) || misaligned(pool->pool_agents, 8) || misaligned(aux, 16) || misaligned(pool->pool_aux, 16)
-        || misaligned(rng, 8) || misaligned(sel->rng_words, 8) || misaligned(step_count, 4) || misaligned(pool->episode, 4)
-        || ((spec->cell_bytes == 0 || spec->cell_bytes == 2) && (misaligned(grid, 2) || misaligned(pool_grid, 2))))
-        return MGX_ERR_INVALID_ARGUMENT;
-    if (spec->cell_bytes < 0 || spec->cell_bytes > 3) return MGX_ERR_INVALID_ARGUMENT;
-    const int HW3 = spec->width * spec->height * (spec->cell_bytes == 1 ? 1 : (spec->cell_bytes == 3 ? 3 : kCellBytes));   // bytes of one env's grid
-    const int64_t blocks = (batch + 255) / 256;
-    if (blocks > INT_MAX) return MGX_ERR_UNSUPPORTED;
-    const ResetUnit ru = reset_copy_unit(HW3, reinterpret_cast<uintptr_t>(grid), reinterpret_cast<uintptr_t>(pool_grid));   // (mgx_aux_geom.h)
-    const int unit = ru.unit, units = ru.units;
-    const uint32_t inv_units = (uint32_t)(((1ull << 32) + units - 1) / units);
-    const uint32_t inv_A = (uint32_t)(((1ull << 32) + spec->num_agents - 1) / spec->num_agents);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-#define MGX_RESET(T)                                                                                                   \
-    hipLaunchKernelGGL(reset_select_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, HW3, spec->num_agents, batch,  \
-                       pool->first_env, pool->pool_size, inv_units, inv_A, sel->select, sel->rng_words, pool_grid,      \
-                       pool->pool_agents, pool->pool_aux, grid, agents, rng, step_count, aux, pool->episode, pool->was_reset)
-    switch (unit) {
-    case 16: MGX_RESET(uint4); break;
-    case 8:  MGX_RESET(uint64_t); break;
-    case 4:  MGX_RESET(uint32_t); break;
-    case 2:  MGX_RESET(uint16_t); break;
-    default: MGX_RESET(uint8_t); break;
-    }
-#undef MGX_RESET
+    if (!sel || !pool) return MGX_ERR_INVALID_ARGUMENT;
+    PoolLaunch pl;
+    const int rc = check_reset_pool(spec, batch, *pool, grid, agents, rng, sel->rng_words, step_count, aux, pl);
+    if (rc || batch == 0) return rc;
+    hipLaunchKernelGGL(MGX_BY_UNIT(reset_select_kernel, pl.unit), pl.blocks, dim3(256), 0, static_cast<hipStream_t>(stream), pl.HWB,
+                       spec->num_agents, batch, pool->first_env, pool->pool_size, pl.inv_units, pl.inv_A, sel->select, sel->rng_words,
+                       reinterpret_cast<const uint8_t *>(pool->pool_grid), pool->pool_agents, pool->pool_aux,
+                       reinterpret_cast<uint8_t *>(grid), agents, rng, step_count, aux, pool->episode, pool->was_reset);
     return finish_launch();
 }
 

@@ -6,7 +6,20 @@
 
 #include <stdint.h>
 
+#include "../../include/mgx.h"
+
 namespace mgx {
+
+// Division by multiplication, the one form these kernels use: __umulhi(n, recip32(d)) for n / d.
+// recip32(d) = ceil(2^32 / d), d >= 2.  (d == 1 is not representable -- 2^32 comes out as 0 --: the kernels branch, as copy_layouts
+// does at units == 1 and the granule kernels at gpe == 1.)
+inline uint32_t recip32(uint32_t d) { return (uint32_t)((((uint64_t)1 << 32) + d - 1) / d); }
+// __umulhi(n, recip32(d)) == n / d for every n below this (d >= 2).  With e = recip32(d) * d - 2^32 in [0, d) the product is
+// n / d + n * e / (d * 2^32): its floor is the quotient's while n * e < 2^32, and the first n = d - 1 (mod d) beyond that is wrong.
+inline uint64_t recip32_exact_below(uint32_t d) {
+    const uint64_t two32 = (uint64_t)1 << 32, e = (uint64_t)recip32(d) * d - two32;
+    return e == 0 ? two32 : (two32 + e - 1) / e;
+}
 
 // one_hot: a workgroup takes chunks of kOhCells cells; at most 4096 workgroups, the rest by a grid-stride loop
 constexpr int kOhCells = 1024;
@@ -58,6 +71,20 @@ inline ResetUnit reset_copy_unit(int env_bytes, uintptr_t grid, uintptr_t pool_g
     while (r.unit > 1 && (env_bytes % r.unit || (grid & (uintptr_t)(r.unit - 1)) || (pool_grid & (uintptr_t)(r.unit - 1)))) r.unit >>= 1;
     r.units = env_bytes / r.unit;
     return r;
+}
+
+// persistent stepping: granules (4 action bytes each) per env and in all, and the reciprocal the producer kernels find a granule's
+// env with -- g / gpe by recip32, so the batch ends where that stops being exact (recip32_exact_below: 2^30 granules at gpe = 5,
+// 1 431 655 766 at gpe = 7, beyond 2^31 at every other gpe <= 8) or at 2^31 granules, whichever comes first
+inline int granule_geometry(const MgxSpec *spec, int64_t batch, int &gpe, uint32_t &inv_gpe, int64_t &ng) {
+    if (!spec || batch < 1 || spec->num_agents < 1 || spec->num_agents > MGX_MAX_AGENTS) return MGX_ERR_INVALID_ARGUMENT;
+    gpe = (spec->num_agents + 3) / 4;
+    ng = batch * gpe;
+    int64_t limit = (int64_t)1 << 31;
+    if (gpe > 1 && (int64_t)recip32_exact_below((uint32_t)gpe) < limit) limit = (int64_t)recip32_exact_below((uint32_t)gpe);
+    if (ng >= limit) return MGX_ERR_UNSUPPORTED;
+    inv_gpe = recip32((uint32_t)gpe);
+    return MGX_OK;
 }
 
 }  // namespace mgx

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "mgx_fused.h"
+#include "mgx_host.h"
 
 #if MGX_SINGLE_TU      // (tools' builds that need the kernels and the host code in one module, e.g. -DMGX_SPANS=1: kernel-side
                        // globals); -DMGX_ONLY_V=<v> keeps just that view size (a third of the build time)
@@ -228,8 +229,6 @@ int plan_launch(LaunchPlan &lp, const MgxSpec &sp, int64_t batch, LaunchForm for
     if (lp.nwg > INT_MAX) return MGX_ERR_UNSUPPORTED;
     return MGX_OK;
 }
-
-inline bool misaligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
 
 // The state / input / output tensors of a stepping launch (include/mgx.h: MgxStepArgs): there where the spec needs them, aligned.
 // (the persistent launch takes its actions as granules: MgxPersistent)

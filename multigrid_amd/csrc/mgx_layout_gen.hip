@@ -24,9 +24,8 @@
 #include <limits.h>
 #include <stdint.h>
 
+#include "mgx_host.h"
 #include "mgx_layout_gen.h"
-
-extern "C" void mgx_internal_set_hip_error(int e);      // mgx_kernels.hip: what mgx_last_hip_error() reports
 
 namespace {
 
@@ -46,32 +45,44 @@ struct GenArgs {
     uint8_t *was_reset;
 };
 
-__global__ __launch_bounds__(64) void reset_generate_kernel(const GenArgs a) {
+// The generation, once for both triggers: the done test, or (BY_SELECT, include/mgx.h: mgx_reset_generate_select) the caller's choice
+// -- one `select` byte per env, NULL = every env --, so a wavefront nobody was chosen in ends after one byte load per lane; an env
+// that is not chosen is left exactly as it is, finished or not: only its was_reset byte is cleared.  `rng_words` (BY_SELECT only;
+// NULL: np_random runs on): the chosen env's np_random becomes a FRESH generator for this generation (reset(seed=...), base.py:269)
+// -- its PCG64 words, no pending 32-bit half.  The placement stream gen_state[0..4] is the construction-time generator, which
+// reset(seed) does not replace.
+template <bool BY_SELECT>
+__device__ __forceinline__ void generate_restarts(const GenArgs &a, const uint8_t *select, const uint64_t *rng_words) {
     extern __shared__ uint8_t lds[];
     const int lane = threadIdx.x;
     const int W = a.sp.width, H = a.sp.height, A = a.sp.num_agents, HWB = H * W * kCellBytes;
     const int64_t e0 = (int64_t)blockIdx.x * 64;
     const int64_t b = e0 + lane;
-    bool done = false;
+    bool chosen = false;
     if (b < a.batch) {
-        const uint64_t *rows = reinterpret_cast<const uint64_t *>(a.agents) + b * A;
-        bool all_term = true;
-        for (int k = 0; k < A; ++k) all_term &= row_term(rows[k]);
-        done = all_term || a.step_count[b] >= a.sp.max_steps;                        // base.py:534-539
-        if (a.was_reset) a.was_reset[b] = (uint8_t)done;
+        if constexpr (BY_SELECT) {
+            chosen = select == nullptr || select[b] != 0;
+        } else {
+            const uint64_t *rows = reinterpret_cast<const uint64_t *>(a.agents) + b * A;
+            bool all_term = true;
+            for (int k = 0; k < A; ++k) all_term &= row_term(rows[k]);
+            chosen = all_term || a.step_count[b] >= a.sp.max_steps;                  // base.py:534-539
+        }
+        if (a.was_reset) a.was_reset[b] = (uint8_t)chosen;
     }
-    const uint64_t mask = __builtin_amdgcn_ballot_w64(done);
+    const uint64_t mask = __builtin_amdgcn_ballot_w64(chosen);
     if (mask == 0) return;
     copy_blank(a.gen, a.grid, e0, HWB, mask, lane);                                  // (1) all lanes
     // (2) overwrites cells that OTHER lanes of this wavefront have just stored: their stores must have left the wave first
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_s_waitcnt(0x0F70);                                              // vmcnt(0)
     __builtin_amdgcn_wave_barrier();
-    if (!done) return;
+    if (!chosen) return;
     NpGen lay, npr;                                                                  // (2) the owning lane
     uint64_t *gs = a.gen.gen_state + b * 6;
-    for (int k = 0; k < 4; ++k) { lay.s[k] = gs[k]; npr.s[k] = a.rng[b * 4 + k]; }
-    lay.buf = gs[4]; npr.buf = gs[5];
+    const uint64_t *nw = rng_words ? rng_words + b * 4 : a.rng + b * 4;
+    for (int k = 0; k < 4; ++k) { lay.s[k] = gs[k]; npr.s[k] = nw[k]; }
+    lay.buf = gs[4]; npr.buf = rng_words ? 0 : gs[5];
     const uint4 aux = generate_episode(a.gen, W, H, A, lay, npr, lds + lane * (2 * A), a.grid + b * HWB,
                                        reinterpret_cast<uint64_t *>(a.agents) + b * A);
     if (a.aux) reinterpret_cast<uint4 *>(a.aux)[b] = aux;
@@ -81,6 +92,14 @@ __global__ __launch_bounds__(64) void reset_generate_kernel(const GenArgs a) {
     a.episode[b] += 1;
 }
 
+struct GenSelectArgs {
+    GenArgs g;
+    const uint8_t *select;
+    const uint64_t *rng_words;
+};
+
+__global__ __launch_bounds__(64) void reset_generate_kernel(const GenArgs a) { generate_restarts<false>(a, nullptr, nullptr); }
+__global__ __launch_bounds__(64) void reset_generate_select_kernel(const GenSelectArgs s) { generate_restarts<true>(s.g, s.select, s.rng_words); }
 
 // MgxGenStage.candidates (include/mgx.h): kGroupLanes lanes per (env, value of the generator's env.np_random draw) -- a group makes ONE
 // candidate, its lanes the tries of every place_obj call at once (mgx_layout_gen.h: GroupCtx; rounds 5: one lane per candidate, the
@@ -135,52 +154,31 @@ __global__ __launch_bounds__(64) void stage_candidates_kernel(const GenArgs a) {
     st.tag[b * 4 + k] = a.episode[b];
 }
 
-// mgx_reset_generate_select (include/mgx.h): reset_generate_kernel with the done test replaced by the caller's choice -- one byte
-// per env (`select == NULL`: every env), so a wavefront nobody was chosen in ends after one byte load per lane.  An env that is not
-// chosen is left exactly as it is, finished or not; only its was_reset byte is cleared.  `rng_words`: the chosen env's np_random
-// becomes a FRESH generator for this generation (reset(seed=...), base.py:269): its PCG64 words, no pending 32-bit half.  The
-// placement stream gen_state[0..4] is the construction-time generator, which reset(seed) does not replace.
-struct GenSelectArgs {
-    GenArgs g;
-    const uint8_t *select;
-    const uint64_t *rng_words;
-};
-
-__global__ __launch_bounds__(64) void reset_generate_select_kernel(const GenSelectArgs s) {
-    extern __shared__ uint8_t lds[];
-    const GenArgs &a = s.g;
-    const int lane = threadIdx.x;
-    const int W = a.sp.width, H = a.sp.height, A = a.sp.num_agents, HWB = H * W * kCellBytes;
-    const int64_t e0 = (int64_t)blockIdx.x * 64;
-    const int64_t b = e0 + lane;
-    bool sel = false;
-    if (b < a.batch) {
-        sel = s.select == nullptr || s.select[b] != 0;
-        if (a.was_reset) a.was_reset[b] = (uint8_t)sel;
-    }
-    const uint64_t mask = __builtin_amdgcn_ballot_w64(sel);
-    if (mask == 0) return;
-    copy_blank(a.gen, a.grid, e0, HWB, mask, lane);                                  // (1) all lanes
-    // (2) overwrites cells that OTHER lanes of this wavefront have just stored: their stores must have left the wave first
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_s_waitcnt(0x0F70);                                              // vmcnt(0)
-    __builtin_amdgcn_wave_barrier();
-    if (!sel) return;
-    NpGen lay, npr;                                                                  // (2) the owning lane
-    uint64_t *gs = a.gen.gen_state + b * 6;
-    const uint64_t *nw = s.rng_words ? s.rng_words + b * 4 : a.rng + b * 4;
-    for (int k = 0; k < 4; ++k) { lay.s[k] = gs[k]; npr.s[k] = nw[k]; }
-    lay.buf = gs[4]; npr.buf = s.rng_words ? 0 : gs[5];                              // (a fresh generator has no pending half)
-    const uint4 aux = generate_episode(a.gen, W, H, A, lay, npr, lds + lane * (2 * A), a.grid + b * HWB,
-                                       reinterpret_cast<uint64_t *>(a.agents) + b * A);
-    if (a.aux) reinterpret_cast<uint4 *>(a.aux)[b] = aux;
-    for (int k = 0; k < 4; ++k) { gs[k] = lay.s[k]; a.rng[b * 4 + k] = npr.s[k]; }
-    gs[4] = lay.buf; gs[5] = npr.buf;
-    a.step_count[b] = 0;                                                             // base.py:292
-    a.episode[b] += 1;
+// What mgx_reset_generate and mgx_reset_generate_select check alike (MGX_OK at batch > 0: ready to launch).
+int check_reset_generate(const MgxSpec *spec, int64_t batch, const MgxLayoutGen *gen, const void *grid, const uint8_t *agents,
+                         const uint64_t *rng, const uint64_t *rng_words, const int32_t *step_count, const uint8_t *aux,
+                         const int32_t *episode) {
+    if (!spec || !gen || batch < 0) return MGX_ERR_INVALID_ARGUMENT;
+    if (spec->width < 3 || spec->height < 3 || spec->num_agents < 1 || spec->num_agents > MGX_MAX_AGENTS)
+        return MGX_ERR_INVALID_ARGUMENT;
+    if (spec->width > 254 || spec->height > 254) return MGX_ERR_UNSUPPORTED;         // positions are bytes, 0xff = off the grid
+    if (spec->cell_bytes == 1) return MGX_ERR_UNSUPPORTED;                           // (generation writes 16-bit cells)
+    if (batch == 0) return MGX_OK;
+    if (!gen->blank || !gen->gen_state || !grid || !agents || !rng || !step_count || !episode) return MGX_ERR_INVALID_ARGUMENT;
+    if (misaligned(agents, 8) || misaligned(rng, 8) || misaligned(gen->gen_state, 8) || misaligned(aux, 16)
+        || misaligned(step_count, 4) || misaligned(episode, 4) || misaligned(rng_words, 8))
+        return MGX_ERR_INVALID_ARGUMENT;
+    if (const int rc = check_layout_gen(spec, gen)) return rc;
+    if (spec->env_kind != MGX_KIND_EMPTY && !aux) return MGX_ERR_INVALID_ARGUMENT;
+    return (batch + 63) / 64 > INT_MAX ? MGX_ERR_UNSUPPORTED : MGX_OK;
 }
 
-inline bool misaligned(const void *p, uintptr_t al) { return (reinterpret_cast<uintptr_t>(p) & (al - 1)) != 0; }
+// one wavefront per 64 envs, two LDS bytes per (lane, agent)
+template <typename Args>
+int launch_generate(void (*kernel)(const Args), const Args &args, int64_t batch, int A, void *stream) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((batch + 63) / 64)), dim3(64), (size_t)(64 * 2 * A), static_cast<hipStream_t>(stream), args);
+    return finish_launch();
+}
 
 }  // namespace
 
@@ -194,70 +192,34 @@ extern "C" int mgx_internal_stage_candidates(const MgxSpec *spec, int64_t batch,
     const size_t lds = (size_t)(64 * 2 * spec->num_agents);
     hipStream_t hs = static_cast<hipStream_t>(stream);
     switch (gen->kind) {
-    case MGX_GEN_EMPTY_FIXED: hipLaunchKernelGGL(stage_candidates_kernel<MGX_GEN_EMPTY_FIXED>, dim3((unsigned)blocks), dim3(64), lds, hs, ga); break;
-    case MGX_GEN_EMPTY_RANDOM: hipLaunchKernelGGL(stage_candidates_kernel<MGX_GEN_EMPTY_RANDOM>, dim3((unsigned)blocks), dim3(64), lds, hs, ga); break;
-    case MGX_GEN_BLOCKEDUNLOCKPICKUP: hipLaunchKernelGGL(stage_candidates_kernel<MGX_GEN_BLOCKEDUNLOCKPICKUP>, dim3((unsigned)blocks), dim3(64), lds, hs, ga); break;
-    case MGX_GEN_REDBLUEDOORS: hipLaunchKernelGGL(stage_candidates_kernel<MGX_GEN_REDBLUEDOORS>, dim3((unsigned)blocks), dim3(64), lds, hs, ga); break;
-    case MGX_GEN_LOCKEDHALLWAY: hipLaunchKernelGGL(stage_candidates_kernel<MGX_GEN_LOCKEDHALLWAY>, dim3((unsigned)blocks), dim3(64), lds, hs, ga); break;
+#define MGX_STAGE(KIND) case KIND: hipLaunchKernelGGL(stage_candidates_kernel<KIND>, dim3((unsigned)blocks), dim3(64), lds, hs, ga); break
+    MGX_STAGE(MGX_GEN_EMPTY_FIXED); MGX_STAGE(MGX_GEN_EMPTY_RANDOM); MGX_STAGE(MGX_GEN_BLOCKEDUNLOCKPICKUP);
+    MGX_STAGE(MGX_GEN_REDBLUEDOORS); MGX_STAGE(MGX_GEN_LOCKEDHALLWAY);
+#undef MGX_STAGE
     default: return MGX_ERR_UNSUPPORTED;
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { mgx_internal_set_hip_error((int)e); return MGX_ERR_LAUNCH; }
-    return MGX_OK;
+    return finish_launch();
 }
 
 extern "C" {
 
 int mgx_reset_generate(const MgxSpec *spec, int64_t batch, const MgxLayoutGen *gen, MgxCell *grid, uint8_t *agents,
                        uint64_t *rng, int32_t *step_count, uint8_t *aux, int32_t *episode, uint8_t *was_reset, void *stream) {
-    if (!spec || !gen || batch < 0) return MGX_ERR_INVALID_ARGUMENT;
-    if (spec->width < 3 || spec->height < 3 || spec->num_agents < 1 || spec->num_agents > MGX_MAX_AGENTS)
-        return MGX_ERR_INVALID_ARGUMENT;
-    if (spec->width > 254 || spec->height > 254) return MGX_ERR_UNSUPPORTED;         // positions are bytes, 0xff = off the grid
-    if (spec->cell_bytes == 1) return MGX_ERR_UNSUPPORTED;                           // (generation writes 16-bit cells)
-    if (batch == 0) return MGX_OK;
-    if (!gen->blank || !gen->gen_state || !grid || !agents || !rng || !step_count || !episode) return MGX_ERR_INVALID_ARGUMENT;
-    if (misaligned(agents, 8) || misaligned(rng, 8) || misaligned(gen->gen_state, 8) || misaligned(aux, 16)
-        || misaligned(step_count, 4) || misaligned(episode, 4))
-        return MGX_ERR_INVALID_ARGUMENT;
-    const int rc = check_layout_gen(spec, gen);
-    if (rc) return rc;
-    if (spec->env_kind != MGX_KIND_EMPTY && !aux) return MGX_ERR_INVALID_ARGUMENT;
-    const int64_t blocks = (batch + 63) / 64;
-    if (blocks > INT_MAX) return MGX_ERR_UNSUPPORTED;
-    GenArgs ga{*spec, batch, *gen, reinterpret_cast<uint8_t *>(grid), agents, rng, step_count, aux, episode, was_reset};
-    hipLaunchKernelGGL(reset_generate_kernel, dim3((unsigned)blocks), dim3(64), (size_t)(64 * 2 * spec->num_agents),
-                       static_cast<hipStream_t>(stream), ga);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { mgx_internal_set_hip_error((int)e); return MGX_ERR_LAUNCH; }
-    return MGX_OK;
+    const int rc = check_reset_generate(spec, batch, gen, grid, agents, rng, nullptr, step_count, aux, episode);
+    if (rc || batch == 0) return rc;
+    const GenArgs ga{*spec, batch, *gen, reinterpret_cast<uint8_t *>(grid), agents, rng, step_count, aux, episode, was_reset};
+    return launch_generate(reset_generate_kernel, ga, batch, spec->num_agents, stream);
 }
 
 int mgx_reset_generate_select(const MgxSpec *spec, int64_t batch, const MgxResetSelect *sel, const MgxLayoutGen *gen, MgxCell *grid,
                               uint8_t *agents, uint64_t *rng, int32_t *step_count, uint8_t *aux, int32_t *episode,
                               uint8_t *was_reset, void *stream) {
-    if (!spec || !sel || !gen || batch < 0) return MGX_ERR_INVALID_ARGUMENT;
-    if (spec->width < 3 || spec->height < 3 || spec->num_agents < 1 || spec->num_agents > MGX_MAX_AGENTS)
-        return MGX_ERR_INVALID_ARGUMENT;
-    if (spec->width > 254 || spec->height > 254) return MGX_ERR_UNSUPPORTED;         // positions are bytes, 0xff = off the grid
-    if (spec->cell_bytes == 1) return MGX_ERR_UNSUPPORTED;                           // (generation writes 16-bit cells)
-    if (batch == 0) return MGX_OK;
-    if (!gen->blank || !gen->gen_state || !grid || !agents || !rng || !step_count || !episode) return MGX_ERR_INVALID_ARGUMENT;
-    if (misaligned(agents, 8) || misaligned(rng, 8) || misaligned(gen->gen_state, 8) || misaligned(aux, 16)
-        || misaligned(step_count, 4) || misaligned(episode, 4) || misaligned(sel->rng_words, 8))
-        return MGX_ERR_INVALID_ARGUMENT;
-    const int rc = check_layout_gen(spec, gen);
-    if (rc) return rc;
-    if (spec->env_kind != MGX_KIND_EMPTY && !aux) return MGX_ERR_INVALID_ARGUMENT;
-    const int64_t blocks = (batch + 63) / 64;
-    if (blocks > INT_MAX) return MGX_ERR_UNSUPPORTED;
-    GenSelectArgs ga{{*spec, batch, *gen, reinterpret_cast<uint8_t *>(grid), agents, rng, step_count, aux, episode, was_reset},
-                     sel->select, sel->rng_words};
-    hipLaunchKernelGGL(reset_generate_select_kernel, dim3((unsigned)blocks), dim3(64), (size_t)(64 * 2 * spec->num_agents),
-                       static_cast<hipStream_t>(stream), ga);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { mgx_internal_set_hip_error((int)e); return MGX_ERR_LAUNCH; }
-    return MGX_OK;
+    if (!sel) return MGX_ERR_INVALID_ARGUMENT;
+    const int rc = check_reset_generate(spec, batch, gen, grid, agents, rng, sel->rng_words, step_count, aux, episode);
+    if (rc || batch == 0) return rc;
+    const GenSelectArgs ga{{*spec, batch, *gen, reinterpret_cast<uint8_t *>(grid), agents, rng, step_count, aux, episode, was_reset},
+                           sel->select, sel->rng_words};
+    return launch_generate(reset_generate_select_kernel, ga, batch, spec->num_agents, stream);
 }
 
 }  // extern "C"

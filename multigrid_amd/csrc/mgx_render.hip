@@ -17,10 +17,10 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "mgx_aux_geom.h"
+#include "mgx_host.h"
 #include "mgx_render.h"
 #include "mgx_rules.h"
-
-extern "C" void mgx_internal_set_hip_error(int e);      // mgx_kernels.hip: what mgx_last_hip_error() reports
 
 namespace {
 
@@ -42,7 +42,7 @@ __global__ __launch_bounds__(256) void render_atlas_kernel(int ts, int total, Re
     p[2] = (uint8_t)(c >> 16);
 }
 
-// n / d with magic = ceil(2^32 / d): exact while n * d < 2^32 (here n < 2^16, d <= 192)
+// n / d with magic = recip32(d) (mgx_aux_geom.h): here n < W * d <= 255 * d and d = 3 * ts <= 192, inside recip32_exact_below(d)
 __device__ __forceinline__ uint32_t div_small(uint32_t n, uint32_t magic) { return __umulhi(n, magic); }
 
 // CB: bytes per cell (1 compact, 2 MgxCell, 3 byte triples); VEC: 16-byte stores (ts % 4 == 0, aligned); NT: non-temporal.
@@ -129,16 +129,6 @@ __global__ __launch_bounds__(256) void render_kernel(int W, int H, int A, int v,
     }
 }
 
-int finish_launch() {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { mgx_internal_set_hip_error((int)e); return MGX_ERR_LAUNCH; }
-    return MGX_OK;
-}
-
-inline bool misaligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
-inline uint32_t magic(uint32_t d) { return (uint32_t)(((1ull << 32) + d - 1) / d); }
-
 template <int CB>
 using RenderKernel = void (*)(int, int, int, int, int, const uint8_t *, const uint8_t *, const uint8_t *, const uint8_t *, uint8_t *,
                               uint32_t, float);
@@ -174,7 +164,7 @@ int mgx_render(const MgxSpec *spec, int64_t n, const MgxCell *grid, const uint8_
     const bool vec = tile_size % 4 == 0 && !misaligned(frames, 16) && !misaligned(atlas, 4);
     const char *stores = getenv("MGX_RENDER_STORES");
     const bool nt = !(stores && strcmp(stores, "plain") == 0);
-    const uint32_t mT3 = magic((uint32_t)T3);
+    const uint32_t mT3 = recip32((uint32_t)T3);
     const float inv_R = 1.0f / (float)R;
     const auto *gp = reinterpret_cast<const uint8_t *>(grid);
     const dim3 blocks((unsigned)(n * H)), threads(256);

@@ -120,3 +120,24 @@ def one_hot_geom(n_cells):
     out = np.zeros(3, np.int64)
     lib().shim_one_hot_geom(C.c_int64(int(n_cells)), _p(out, C.c_int64))
     return tuple(int(v) for v in out)
+
+
+def recip32(d):
+    """ceil(2^32 / d) as the launchers compute it (csrc/mgx_aux_geom.h), d >= 2"""
+    f = lib().shim_recip32
+    f.restype = C.c_uint32
+    return int(f(C.c_uint32(int(d))))
+
+
+def recip32_exact_below(d):
+    """the first n the header does NOT promise __umulhi(n, recip32(d)) == n // d for"""
+    f = lib().shim_recip32_exact_below
+    f.restype = C.c_uint64
+    return int(f(C.c_uint32(int(d))))
+
+
+def granule_geometry(num_agents, batch):
+    """mgx_persistent_post / _feed's granule arithmetic: (return code, granules per env, their reciprocal, granules in all)"""
+    out = np.zeros(3, np.int64)
+    rc = lib().shim_granule_geometry(int(num_agents), C.c_int64(int(batch)), _p(out, C.c_int64))
+    return (int(rc),) + tuple(int(v) for v in out)

@@ -267,3 +267,18 @@ extern "C" void shim_reset_unit(int env_bytes, uint64_t grid_addr, uint64_t pool
 extern "C" void shim_one_hot_geom(int64_t n_cells, int64_t *out) {
     out[0] = kOhCells; out[1] = one_hot_chunks(n_cells); out[2] = one_hot_blocks(n_cells);
 }
+
+// the reciprocal every division by a launch constant goes through, and the range it is exact over (mgx_aux_geom.h)
+extern "C" uint32_t shim_recip32(uint32_t d) { return recip32(d); }
+extern "C" uint64_t shim_recip32_exact_below(uint32_t d) { return recip32_exact_below(d); }
+
+// mgx_persistent_post / mgx_persistent_feed's granule arithmetic for `num_agents` agents: the return code; out[3] = granules per env,
+// their reciprocal, granules in all
+extern "C" int shim_granule_geometry(int num_agents, int64_t batch, int64_t *out) {
+    MgxSpec sp{};
+    sp.num_agents = num_agents;
+    int gpe = 0; uint32_t inv = 0; int64_t ng = 0;
+    const int rc = granule_geometry(&sp, batch, gpe, inv, ng);
+    out[0] = gpe; out[1] = inv; out[2] = ng;
+    return rc;
+}

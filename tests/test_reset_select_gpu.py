@@ -5,7 +5,8 @@ torch.equal: cells, agents, aux, rng, gen_state, step_count, episode, was_reset 
 Batches of 1, 63 and 130 envs (two full wavefronts and a two-lane tail) under every mask that picks a different path of the scan --
 nobody, everybody, None, lane 0, lane 63, the tail's last lane, every other env, a whole wavefront left out -- with a running env
 among the selected and a finished env among the others; the pool form at 300 envs (a full workgroup and a 44-env wavefront) in every
-copy unit; the staging slots of a staged generator across a reset; and the whole file again on the bounds-checked build."""
+copy unit; the staging slots of a staged generator across a reset; reset_done() against reset(mask=is_done()) -- one body behind two
+triggers -- in both forms; and the whole file again on the bounds-checked build."""
 import ctypes
 import os
 import subprocess
@@ -245,6 +246,57 @@ def test_first_episode_from_reset_alone():
     same_as(envs[0][0], envs[1][0], envs[0][1], envs[1][1], "first episode")
     envs[0][0].step(torch.zeros((130, z.spec.num_agents), dtype=torch.int8, device=DEV), auto_reset=True)
     envs[0][0].check_errors()
+
+
+# ---- one body, two triggers ---------------------------------------------------------------------------------------------------------------
+
+def finish(env, envs):
+    """of `envs`: b % 3 == 0 ends by step_count = max_steps, b % 3 == 1 by every agent's terminated byte, b % 3 == 2 runs on"""
+    b = torch.as_tensor(envs, device=env.cells.device)
+    env.step_count[b[b % 3 == 0]] = env.spec.max_steps
+    env.agents[b[b % 3 == 1], :, 4] = 1
+
+
+def pairs_of_envs(form):
+    """(name, two device envs in the same state with the same finished envs) -- every pool spec at 300 envs: the wavefront of envs
+    128..191 has nobody finished; every generator kind at 130 envs: nobody in wavefront 0, wavefront 1 mixed, env 129 of the two-lane
+    tail finished"""
+    if form == "pool":
+        for name, spec in POOL_SPECS.items():
+            envs = [pool_env(spec, 300, DEV, first_env=4)[0] for _ in range(2)]
+            for e in envs:
+                finish(e, [b for b in range(300) if not 128 <= b < 192])
+            yield name, envs
+    else:
+        for name in GEN_FIXTURES:
+            z, d, spec, gen = load(name)
+            idx = spread(len(z["lay_before"]), 130)
+            envs = [live_env(z, spec, gen, idx, DEV) for _ in range(2)]
+            for e in envs:
+                finish(e, range(64, 130))
+            yield name, envs
+
+
+@pytest.mark.parametrize("form", ["pool", "generator"])
+def test_done_restart_equals_select_of_is_done(form):
+    """reset_done() and reset(mask = is_done()) run the same body behind two triggers: every byte of the state they leave is the same."""
+    for name, (by_done, by_select) in pairs_of_envs(form):
+        done = by_done.is_done()
+        assert torch.equal(done, by_select.is_done())
+        lo = 128 if form == "pool" else 0
+        assert not bool(done[lo:lo + 64].any()) and bool(done[64:128].any()) and not bool(done[64:128].all()), name
+        assert bool(done[-1]) == (form == "generator") and 0 < int(done.sum()) < len(done)
+        for e in (by_done, by_select):
+            e.was_reset.fill_(7)
+        by_done.reset_done()
+        by_select.reset(mask=done.clone())
+        a, b = snapshot(by_done), snapshot(by_select)
+        assert set(a) == set(b) and (form == "pool" or "gen_state" in a)
+        for k in a:
+            assert torch.equal(a[k], b[k]), f"{name}: {k} after reset_done() differs from reset(mask=is_done())"
+        assert torch.equal(by_done.was_reset, by_select.was_reset) and torch.equal(by_done.was_reset.bool(), done), name
+        assert not bool(by_done.is_done().any()), name
+        by_done.check_errors(); by_select.check_errors()
 
 
 # ------------------------------------------------------------------------------------------------------------ bounds-checked build
