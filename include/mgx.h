@@ -620,7 +620,9 @@ int mgx_step_persistent(const MgxSpec *spec, int64_t batch, const MgxStepArgs *a
 /* actions i8[B,A] (as mgx_step takes them) -> the granules of step `step` (counted from 1); stream-ordered behind whatever
  * produced `actions` on `stream`.  This call and mgx_persistent_feed find a granule's env by a 32-bit reciprocal multiply:
  * MGX_ERR_UNSUPPORTED from B * ceil(A/4) = 2^31 granules on, and already from 2^30 at 17..20 agents and from 1 431 655 766 at 25..28
- * (5 and 7 granules per env), where that quotient stops being exact. */
+ * (5 and 7 granules per env), where that quotient stops being exact.
+ * Alignment (MGX_ERR_INVALID_ARGUMENT otherwise): action_granules 8 bytes; `actions` 4 bytes when A is a multiple of 4 (both calls
+ * read an env's actions as dwords then), and for mgx_persistent_feed 2 bytes when A = 2 (it reads them as 16-bit words). */
 int mgx_persistent_post(const MgxSpec *spec, int64_t batch, const int8_t *actions, uint32_t step, uint64_t *action_granules,
                         void *stream);
 /* Returns (in stream order) once done[w] >= step for every w < waves, or after timeout_ms (then ctrl[1] += 1). */
@@ -629,7 +631,9 @@ int mgx_persistent_wait(const uint32_t *done, int32_t waves, uint32_t step, uint
  * action sequence actions i8[T,B,A]
  * through the closed-loop hand-shake -- for t = 1..T: wait for step t-1's outputs to be complete, post the granules of step t --
  * i.e. the shortest producer there can be.  trace (u64[2T + 1], may be NULL): s_memrealtime ticks (100 MHz): [2(t-1)] = step t's
- * predecessor seen complete, [2(t-1) + 1] = step t's granules posted, [2T] = step T seen complete. */
+ * predecessor seen complete, [2(t-1) + 1] = step t's granules posted, [2T] = step T seen complete.  A post's word is stored together
+ * with the word that follows it: when a wait inside the sequence times out, the kernel ends and the words from the last post's on stay as the
+ * caller left them (after steps 1 .. s were posted and step s never completed: [0 .. 2s-2] written, [2s-1 ..] not). */
 int mgx_persistent_feed(const MgxSpec *spec, int64_t batch, const int8_t *actions, int32_t steps, const MgxPersistent *p,
                         int32_t waves, uint64_t *trace, void *stream);
 

@@ -571,12 +571,12 @@ __device__ __forceinline__ bool wait_all_done(const uint32_t *done, int waves, u
     const int stride = (int)blockDim.x;
     for (uint32_t spin = 1;; ++spin) {
         bool ok = true;
-        for (int w0 = 0; w0 < waves; w0 += 8 * stride) {                  // 8 independent loads per thread in flight (sc1: aux 16)
-            uint32_t f[8];
+        for (int w0 = 0; w0 < waves; w0 += kWaitLoads * stride) {         // kWaitLoads independent loads per thread in flight (sc1: aux 16)
+            uint32_t f[kWaitLoads];
 #pragma unroll
-            for (int k = 0; k < 8; ++k) f[k] = __builtin_amdgcn_raw_buffer_load_b32(drs, (int)threadIdx.x * 4, (w0 + k * stride) * 4, 16);
+            for (int k = 0; k < kWaitLoads; ++k) f[k] = __builtin_amdgcn_raw_buffer_load_b32(drs, (int)threadIdx.x * 4, (w0 + k * stride) * 4, 16);
 #pragma unroll
-            for (int k = 0; k < 8; ++k) ok &= (w0 + k * stride + (int)threadIdx.x >= waves) | (f[k] >= step);
+            for (int k = 0; k < kWaitLoads; ++k) ok &= (w0 + k * stride + (int)threadIdx.x >= waves) | (f[k] >= step);
         }
         if (__builtin_amdgcn_ballot_w64(!ok) == 0) break;
         if ((spin & 31u) == 0) {
@@ -592,7 +592,7 @@ __device__ __forceinline__ bool wait_all_done(const uint32_t *done, int waves, u
     return __hip_atomic_load(fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0;
 }
 
-__global__ __launch_bounds__(256) void persistent_wait_kernel(const uint32_t *done, int waves, uint32_t step, uint32_t *ctrl,
+__global__ __launch_bounds__(kWaitThreads) void persistent_wait_kernel(const uint32_t *done, int waves, uint32_t step, uint32_t *ctrl,
                                                               uint32_t timeout_ticks) {
     if (!wait_all_done(done, waves, step, timeout_ticks, ctrl + 4) && threadIdx.x == 0) atomicAdd(ctrl + 1, 1u);
 }
@@ -605,16 +605,17 @@ __global__ __launch_bounds__(256) void persistent_wait_kernel(const uint32_t *do
 // no CU on the chip that can take it -- measured: the hand-shake then runs into its timeout).  One workgroup per slice of 2048
 // granules (at most 32): 8-byte write-through stores leave ONE CU at ~15 GB/s (16384 granules from one workgroup: 9 us per
 // step), so the post is spread; every workgroup sees ALL flags before it posts its slice (the lock-step of a real policy).
-constexpr int kFeedPre = 8, kFeedThreads = 256, kFeedSlice = kFeedPre * kFeedThreads, kFeedMaxWgs = 32;
+// (kFeedPre, kFeedThreads, kFeedSlice, kFeedMaxWgs and the slices' arithmetic: mgx_aux_geom.h, feed_geometry)
+static_assert(kFeedThreads == kWaitThreads, "the feed's workgroups wait with wait_all_done's pass of kWaitPass flags");
 // GB: action bytes a granule takes from the tensor when they are contiguous and aligned -- 4 (A a multiple of 4), 2 (A = 2),
 // 1 (A = 1): granule g's bytes are then the g-th GB-byte word of the step's action tensor; 0 = any other A
 template <int GB>
 __global__ __launch_bounds__(kFeedThreads) void persistent_feed_kernel(const int8_t *__restrict__ actions, int T, int64_t batch, int A, int gpe,
-                                                                       uint32_t inv_gpe, uint64_t *granules, const uint32_t *done, int waves,
-                                                                       uint32_t *ctrl, uint32_t timeout_ticks, uint64_t *trace) {
+                                                                       uint32_t inv_gpe, int64_t per_wg, uint64_t *granules,
+                                                                       const uint32_t *done, int waves, uint32_t *ctrl,
+                                                                       uint32_t timeout_ticks, uint64_t *trace) {
     const int64_t ng_all = batch * gpe, BA = batch * A;
-    // this workgroup's slice of the granules: [g_lo, g_lo + ng)
-    const int64_t per_wg = ((ng_all + gridDim.x - 1) / gridDim.x + 1) & ~(int64_t)1;
+    // this workgroup's slice of the granules: [g_lo, g_lo + ng), per_wg granules from the launcher's feed_geometry
     const int64_t g_lo = (int64_t)blockIdx.x * per_wg;
     const int64_t ng = g_lo >= ng_all ? 0 : (ng_all - g_lo < per_wg ? ng_all - g_lo : per_wg);
     granules += g_lo;
@@ -636,13 +637,19 @@ __global__ __launch_bounds__(kFeedThreads) void persistent_feed_kernel(const int
         }
     };
     fetch(0);
+    // trace: when the last post was complete.  Stored with the NEXT trace word, i.e. once that step's outputs have been waited for: a
+    // producer that gives up leaves no stamp for a step nobody saw complete (include/mgx.h)
+    uint64_t posted = 0;
     for (int t = 0; t < T; ++t) {
         // the outputs of step t (counted from 1) complete?  (nothing to wait for before the first post)
         if (t > 0 && !wait_all_done(done, waves, (uint32_t)t, timeout_ticks, ctrl + 4)) {
             if (threadIdx.x == 0 && lead) { atomicAdd(ctrl + 1, 1u); __hip_atomic_store(ctrl + 0, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
             return;
         }
-        if (trace && threadIdx.x == 0) trace[2 * t] = __builtin_amdgcn_s_memrealtime();
+        if (trace && threadIdx.x == 0) {
+            if (t > 0) trace[2 * t - 1] = posted;
+            trace[2 * t] = __builtin_amdgcn_s_memrealtime();
+        }
         const uint32_t tag = (uint32_t)t + 1u;
         if constexpr (FAST) {
             // one aligned 8-byte write-through store per granule (sc1, aux 16); lanes past the buffer's end are dropped
@@ -680,14 +687,17 @@ __global__ __launch_bounds__(kFeedThreads) void persistent_feed_kernel(const int
         if (trace) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
-            if (threadIdx.x == 0) trace[2 * t + 1] = __builtin_amdgcn_s_memrealtime();
+            posted = __builtin_amdgcn_s_memrealtime();
         }
         if (t + 1 < T) fetch(t + 1);
     }
     // (the last step's outputs: so that "the feed kernel has ended" means "the rollout is complete")
     if (!lead) return;
     if (!wait_all_done(done, waves, (uint32_t)T, timeout_ticks, ctrl + 4) && threadIdx.x == 0) atomicAdd(ctrl + 1, 1u);
-    if (trace && threadIdx.x == 0) trace[2 * T] = __builtin_amdgcn_s_memrealtime();
+    if (trace && threadIdx.x == 0) {
+        trace[2 * T - 1] = posted;
+        trace[2 * T] = __builtin_amdgcn_s_memrealtime();
+    }
 }
 
 // a restart kernel's instantiation for a copy unit of 16 / 8 / 4 / 2 / 1 bytes (mgx_aux_geom.h: reset_copy_unit)
@@ -740,7 +750,7 @@ int mgx_persistent_post(const MgxSpec *spec, int64_t batch, const int8_t *action
 
 int mgx_persistent_wait(const uint32_t *done, int32_t waves, uint32_t step, uint32_t *ctrl, int32_t timeout_ms, void *stream) {
     if (!done || !ctrl || waves < 1 || timeout_ms < 1 || timeout_ms > 30000) return MGX_ERR_INVALID_ARGUMENT;
-    hipLaunchKernelGGL(persistent_wait_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), done, (int)waves, step, ctrl,
+    hipLaunchKernelGGL(persistent_wait_kernel, dim3(1), dim3(kWaitThreads), 0, static_cast<hipStream_t>(stream), done, (int)waves, step, ctrl,
                        (uint32_t)timeout_ms * 100000u);
     return finish_launch();
 }
@@ -751,15 +761,15 @@ int mgx_persistent_feed(const MgxSpec *spec, int64_t batch, const int8_t *action
     const int rc = granule_geometry(spec, batch, gpe, inv, ng);
     if (rc) return rc;
     if (!actions || !p || !p->action_granules || !p->done || !p->ctrl || steps < 1 || waves < 1 || p->timeout_ms < 1
-        || p->timeout_ms > 30000 || misaligned(trace, 8) || ((spec->num_agents & 3) == 0 && misaligned(actions, 4)))
-        return MGX_ERR_INVALID_ARGUMENT;
+        || p->timeout_ms > 30000 || misaligned(trace, 8) || misaligned(p->action_granules, 8)
+        || ((spec->num_agents & 3) == 0 && misaligned(actions, 4)) || (spec->num_agents == 2 && misaligned(actions, 2)))
+        return MGX_ERR_INVALID_ARGUMENT;                                    // (A = 2: the kernel reads the tensor as 16-bit words)
     const int A_ = spec->num_agents;
     auto kern = (A_ & 3) == 0 ? persistent_feed_kernel<4> : A_ == 2 ? persistent_feed_kernel<2> : A_ == 1 ? persistent_feed_kernel<1>
                                                                                                    : persistent_feed_kernel<0>;
-    int64_t nwg = (ng + kFeedSlice - 1) / kFeedSlice;
-    if (nwg > kFeedMaxWgs) nwg = kFeedMaxWgs;
-    hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(kFeedThreads), 0, static_cast<hipStream_t>(stream), actions, (int)steps, batch,
-                       spec->num_agents, gpe, inv, const_cast<uint64_t *>(p->action_granules), p->done, (int)waves, p->ctrl,
+    const FeedGeom fg = feed_geometry(ng);
+    hipLaunchKernelGGL(kern, dim3((unsigned)fg.nwg), dim3(kFeedThreads), 0, static_cast<hipStream_t>(stream), actions, (int)steps, batch,
+                       spec->num_agents, gpe, inv, fg.per_wg, const_cast<uint64_t *>(p->action_granules), p->done, (int)waves, p->ctrl,
                        (uint32_t)p->timeout_ms * 100000u, trace);
     return finish_launch();
 }

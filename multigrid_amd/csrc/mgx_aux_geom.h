@@ -1,6 +1,7 @@
-// mgx_aux_geom.h -- the host-side launch arithmetic of the streaming kernels in mgx_aux.hip, in one place and without any HIP
-// dependency: the launchers call these functions, and tests/hostshim exports them so that tests/test_aux_branch_census.py derives
-// which kernel paths a shape reaches from the SAME arithmetic (not from a Python copy of it).
+// mgx_aux_geom.h -- the host-side launch arithmetic of the streaming kernels and of the persistent hand-shake's producer kernels in
+// mgx_aux.hip, in one place and without any HIP dependency: the launchers call these functions, and tests/hostshim exports them so that
+// tests/test_aux_branch_census.py and tests/test_persist_branch_census.py derive which kernel paths a shape reaches from the SAME
+// arithmetic (not from a Python copy of it).
 #ifndef MGX_AUX_GEOM_H
 #define MGX_AUX_GEOM_H
 
@@ -86,6 +87,27 @@ inline int granule_geometry(const MgxSpec *spec, int64_t batch, int &gpe, uint32
     inv_gpe = recip32((uint32_t)gpe);
     return MGX_OK;
 }
+
+// persistent_feed: kFeedThreads threads per workgroup, kFeedPre granules per thread in registers = one chunk of kFeedSlice granules;
+// one workgroup per kFeedSlice granules, at most kFeedMaxWgs (why: mgx_aux.hip, above the kernel).  Workgroup i posts the granules
+// [i * per_wg, min((i + 1) * per_wg, ng_all)), per_wg rounded up to an even number: no workgroup is left without granules
+// (tests/test_persist_branch_census.py walks every ng_all up to 200 000).
+constexpr int kFeedPre = 8, kFeedThreads = 256, kFeedSlice = kFeedPre * kFeedThreads, kFeedMaxWgs = 32;
+
+struct FeedGeom {
+    int64_t nwg, per_wg;    // workgroups, granules per workgroup (the last one: what is left)
+};
+
+inline FeedGeom feed_geometry(int64_t ng_all) {
+    FeedGeom g;
+    g.nwg = (ng_all + kFeedSlice - 1) / kFeedSlice;
+    if (g.nwg > kFeedMaxWgs) g.nwg = kFeedMaxWgs;
+    g.per_wg = ((ng_all + g.nwg - 1) / g.nwg + 1) & ~(int64_t)1;
+    return g;
+}
+
+// persistent_wait (and the feed's waits): ONE workgroup of kWaitThreads threads looks at kWaitLoads flags per thread and pass
+constexpr int kWaitLoads = 8, kWaitThreads = 256, kWaitPass = kWaitLoads * kWaitThreads;
 
 }  // namespace mgx
 

@@ -141,3 +141,25 @@ def granule_geometry(num_agents, batch):
     out = np.zeros(3, np.int64)
     rc = lib().shim_granule_geometry(int(num_agents), C.c_int64(int(batch)), _p(out, C.c_int64))
     return (int(rc),) + tuple(int(v) for v in out)
+
+
+def feed_geometry(ng_all):
+    """mgx_persistent_feed's launch for `ng_all` granules (csrc/mgx_aux_geom.h): dict(nwg, per_wg, slice, threads, pre, max_wgs)"""
+    out = np.zeros(6, np.int64)
+    lib().shim_feed_geometry(C.c_int64(int(ng_all)), _p(out, C.c_int64))
+    return dict(zip(("nwg", "per_wg", "slice", "threads", "pre", "max_wgs"), (int(v) for v in out)))
+
+
+def feed_first_empty_slice(lo, hi):
+    """the first ng_all in [lo, hi] whose launch holds a workgroup without granules, or None"""
+    f = lib().shim_feed_first_empty_slice
+    f.restype = C.c_int64
+    v = int(f(C.c_int64(int(lo)), C.c_int64(int(hi))))
+    return None if v < 0 else v
+
+
+def wait_geometry():
+    """persistent_wait's pass (csrc/mgx_aux_geom.h): (loads per thread, threads, flags per pass)"""
+    out = np.zeros(3, np.int32)
+    lib().shim_wait_geometry(_p(out, C.c_int32))
+    return tuple(int(v) for v in out)

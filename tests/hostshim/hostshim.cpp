@@ -282,3 +282,23 @@ extern "C" int shim_granule_geometry(int num_agents, int64_t batch, int64_t *out
     out[0] = gpe; out[1] = inv; out[2] = ng;
     return rc;
 }
+
+// mgx_persistent_feed's launch (mgx_aux_geom.h: feed_geometry) for `ng_all` granules, for tests/test_persist_branch_census.py.
+// out[6] = workgroups, granules per workgroup, then the constants: granules per register chunk (kFeedSlice), threads per workgroup,
+// granules per thread and chunk, the cap on the workgroups
+extern "C" void shim_feed_geometry(int64_t ng_all, int64_t *out) {
+    const FeedGeom g = feed_geometry(ng_all);
+    out[0] = g.nwg; out[1] = g.per_wg; out[2] = kFeedSlice; out[3] = kFeedThreads; out[4] = kFeedPre; out[5] = kFeedMaxWgs;
+}
+
+// the first ng_all in [lo, hi] at which some workgroup of the feed's launch gets no granules (g_lo >= ng_all), or -1: none
+extern "C" int64_t shim_feed_first_empty_slice(int64_t lo, int64_t hi) {
+    for (int64_t ng = lo; ng <= hi; ++ng) {
+        const FeedGeom g = feed_geometry(ng);
+        if ((g.nwg - 1) * g.per_wg >= ng) return ng;
+    }
+    return -1;
+}
+
+// persistent_wait's pass: out[3] = loads per thread, threads, flags per pass
+extern "C" void shim_wait_geometry(int32_t *out) { out[0] = kWaitLoads; out[1] = kWaitThreads; out[2] = kWaitPass; }

@@ -3,7 +3,11 @@ alignment, group and tail path, against plain NumPy references written from the 
 
 Every assertion is byte-exact.  The C ABI is called directly (ctypes) so that pointers can be offset; every tensor the kernels touch
 sits between guard bytes that must come back unchanged.  Which kernel paths the cases reach is derived and asserted on the CPU by
-tests/test_aux_branch_census.py."""
+tests/test_aux_branch_census.py.
+
+The other kernels of that file -- the persistent hand-shake's producers persistent_post, persistent_wait and persistent_feed -- are
+walked the same way by tests/test_persist_producers_gpu.py, which borrows `Buf` from here (cases: tests/persist_cases.py, census:
+tests/test_persist_branch_census.py, refusals: tests/test_persist_refusals.py)."""
 import ctypes as C
 
 import numpy as np
