@@ -536,6 +536,23 @@ typedef struct MgxStepArgs {
 
 int mgx_step_ex(const MgxSpec *spec, int64_t batch, const MgxStepArgs *args, void *stream);
 
+/* The step with a per-env LAYOUT MARKER (no ABI change: a new entry, every struct as it was).  An env that has not been written
+ * since its last restart from the layout pool holds, byte for byte, one of the pool's layouts -- an Empty env for ever, any env
+ * between two pickups / drops / toggles -- and the pool is small enough to stay in the caches: such an env's grid need not be
+ * read from device memory at all.
+ *   grid_layout  i32[B], caller-owned state, in/out, 4-byte aligned: k >= 0 = env b's `grid` equals pool_grid[k] bit for bit;
+ *                -1 = nothing is known.  The marker is only a PROMISE about `grid`, which stays valid and current at all times:
+ *                whoever writes an env's grid by any other way (another entry point, a copy, a torch op) stores -1 first.
+ *                Arm it by comparing the grids with the pool once, or start at -1 and let the restarts arm it.
+ * It is mgx_step_ex(spec, batch, args, stream) with that marker kept by the launch: a restart from the pool stores the layout's
+ * index, every cell written back to `grid` stores -1.  Launches of the throughput family (more than 2048 wavefronts) with a
+ * one-layout pool also READ it: a wavefront whose envs all carry the same k >= 0 fetches that layout once from the pool instead
+ * of its envs' grids (grids of a power-of-two size up to 1 KiB; every other wavefront and every other launch loads the grids as
+ * mgx_step_ex does).  Same results bit for bit as long as the promise holds.
+ * Needs args->auto_reset (the pool), steps == 1, no generate and 16-bit cells: MGX_ERR_UNSUPPORTED otherwise.
+ * grid_layout == NULL: exactly mgx_step_ex. */
+int mgx_step_tracked(const MgxSpec *spec, int64_t batch, const MgxStepArgs *args, int32_t *grid_layout, void *stream);
+
 /* Sub-shard stepping.  A launch that fills the chip in one round of wavefronts first loads (no wave has data to work on), then
  * computes, then drains, and the next step's launch cannot start before the last wave has gone; envs are independent, so the
  * same step can be issued as `parts` launches over consecutive blocks of the batch on `parts` streams, and consecutive calls

@@ -25,7 +25,7 @@ EXPORTS = ("mgx_abi_version", "mgx_error_string", "mgx_last_hip_error", "mgx_gen
            "mgx_launch_info", "mgx_one_hot", "mgx_full_obs", "mgx_reset_done", "mgx_rollout", "mgx_step_autoreset",
            "mgx_rollout_autoreset", "mgx_gen_obs_one_hot", "mgx_step_one_hot",
            "mgx_reset_generate", "mgx_step_generate", "mgx_pack_grid", "mgx_unpack_grid",
-           "mgx_step_ex", "mgx_step_chains", "mgx_sub_shards",
+           "mgx_step_ex", "mgx_step_tracked", "mgx_step_chains", "mgx_sub_shards",
            "mgx_pack_grid_env", "mgx_check_grid", "mgx_pack_grid8_env", "mgx_unpack_grid8", "mgx_shape_key", "mgx_shape_register", "mgx_stage_generate",
            "mgx_persistent_waves", "mgx_step_persistent", "mgx_persistent_post", "mgx_persistent_wait", "mgx_persistent_feed",
            "mgx_rollout_info", "mgx_render_atlas", "mgx_render", "mgx_reset_select", "mgx_reset_generate_select")
@@ -157,6 +157,11 @@ def lib() -> C.CDLL:
     L.mgx_launch_info.argtypes = [C.POINTER(MgxSpecC), i64, C.POINTER(MgxLaunchInfo)]
     L.mgx_step_ex.restype = C.c_int
     L.mgx_step_ex.argtypes = [C.POINTER(MgxSpecC), i64, C.POINTER(MgxStepArgs), vp]
+    # (another build loaded through MGX_LIBMGX -- the A/B tools compare against older libraries -- may lack the entry: the env then
+    # steps untracked, ops.HipBackend.bind_step; the product library without it fails right here)
+    if is_product_lib() or hasattr(L, "mgx_step_tracked"):
+        L.mgx_step_tracked.restype = C.c_int
+        L.mgx_step_tracked.argtypes = [C.POINTER(MgxSpecC), i64, C.POINTER(MgxStepArgs), vp, vp]
     L.mgx_step_chains.restype = C.c_int
     L.mgx_step_chains.argtypes = [C.POINTER(MgxSpecC), i64, C.POINTER(MgxStepArgs), C.c_int32, C.POINTER(vp), vp]
     L.mgx_sub_shards.restype = C.c_int

@@ -36,6 +36,8 @@ class StepGraph:
         if self.env._layout_version != self._version:
             raise RuntimeError("this graph was captured before set_layout_pool() / set_layout_generator() replaced the layout "
                                "tensors it holds pointers to: capture_steps() again")
+        if not getattr(self, "_tracked", False):     # (steps that write cells without keeping the layout marker)
+            self.env._disarm()
         self.graph.replay()
 
 
@@ -78,7 +80,7 @@ class PersistentSession:
         self.waited = 0                  # steps waited for
         self.open = False
         ar = env._auto_reset_args(self.auto_reset, getattr(env, "was_reset", None))
-        self._sa, self._keep = be.step_args(env.cells, env.agents, env.rng, env.step_count,
+        self._sa, self._keep = be.step_args(env._cells, env.agents, env.rng, env.step_count,
                                             env.aux if env.spec.env_kind != "empty" else None, env.err, env.obs, env.dir,
                                             env.reward, env.terminated, env.truncated, auto_reset=ar)
         self._pers = be.persistent_struct(self.granules, self.done, self.ctrl, self.max_steps, self.timeout_ms)
@@ -89,6 +91,7 @@ class PersistentSession:
         env.join()
         if env._session is not None:
             raise RuntimeError("this env already has a persistent session open")
+        env._disarm()                                      # (the launch writes the grids back without keeping the layout marker)
         cur = torch.cuda.current_stream(env.device)
         self.stream.wait_stream(cur)                       # (the state and the zeroed hand-shake words are in place)
         env.backend.persistent_launch(env.batch, self._sa, self._pers, self.stream.cuda_stream)
@@ -101,9 +104,9 @@ class PersistentSession:
         env = self.env
         if not self.open or self.t >= self.max_steps:
             raise RuntimeError("the persistent session is closed or has used up its max_steps")
-        if actions.dtype is not torch.int8 or actions.shape != env._act_shape or actions.device != env.cells.device \
+        if actions.dtype is not torch.int8 or actions.shape != env._act_shape or actions.device != env._cells.device \
                 or not actions.is_contiguous():
-            raise ValueError(f"actions must be a contiguous int8 tensor of shape {tuple(env._act_shape)} on {env.cells.device}")
+            raise ValueError(f"actions must be a contiguous int8 tensor of shape {tuple(env._act_shape)} on {env._cells.device}")
         self.t += 1
         env.backend.persistent_post(env.batch, actions, self.t, self.granules)
 
@@ -196,7 +199,13 @@ class BatchedMultiGridEnv:
         B, A, dev = self.batch, spec.num_agents, self.device
         # packed cells: MgxCell bit patterns (i16), or -- spec.cell_bytes == 1 -- the compact MgxCell8 bytes (include/mgx.h)
         # (spec.cell_bytes == 3: the reference's byte triples themselves, u8[B,H,W,3])
-        self.cells = torch.zeros(spec.cells_shape(B), dtype=torch.uint8 if spec.cell_bytes != 2 else torch.int16, device=dev)
+        self._cells = torch.zeros(spec.cells_shape(B), dtype=torch.uint8 if spec.cell_bytes != 2 else torch.int16, device=dev)
+        # the layout marker (include/mgx.h: mgx_step_tracked): i32[B], k >= 0 = env b's cells equal layout k of the pool bit for bit,
+        # -1 = unknown.  `_mark` is shared with the sub-shards of split(): "armed" = the marker may hold a k >= 0 (only then does a
+        # path that writes cells behind its back pay the fill that takes the promise back: _disarm), "graphs" = a captured graph
+        # holds tracked steps (it re-arms whenever it is replayed: "armed" then stays up), "root" = the whole tensor
+        self._marker = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        self._mark = {"armed": False, "graphs": False, "root": self._marker}
         self.agents = torch.zeros(spec.agents_shape(B), dtype=torch.uint8, device=dev)
         self.rng = torch.zeros((B, 4), dtype=torch.int64, device=dev)
         self.step_count = torch.zeros((B,), dtype=torch.int32, device=dev)
@@ -240,14 +249,67 @@ class BatchedMultiGridEnv:
         return self.shape_kernel
 
     @property
+    def cells(self) -> torch.Tensor:
+        """The packed grid cells (i16[B,H,W]; u8 for the compact / byte formats) -- the env's own tensor, for callers that read or
+        WRITE it in place (the torch ops, a cell edit).  Handing it out takes back everything the layout marker promises about it
+        (one fill, and only while the marker is armed): write through a reference taken earlier than the last `step()` and the
+        next step may not see it.  The env's own methods use `_cells`."""
+        self._disarm()
+        return self._cells
+
+    # ------------------------------------------------------------------------------------------ layout marker
+    def _tracks(self) -> bool:
+        """The steps of this env can keep the layout marker: 16-bit cells, restarts from a layout pool."""
+        return getattr(self, "_pool", None) is not None and getattr(self, "_gen", None) is None and self.spec.cell_bytes == 2
+
+    def _disarm(self):
+        """Something is about to write cells without keeping the marker (a rollout, a persistent launch, a step without
+        auto-reset, a torch op on `cells`, ...): nothing is known about any env's grid any more.  No kernel unless armed."""
+        m = self._mark
+        if m["armed"]:
+            m["root"].fill_(-1)
+            # (while a graph is captured the fill is only recorded, and a captured graph of tracked steps re-arms whenever it is
+            # replayed: the flag then stays up)
+            if not m["graphs"] and not (self.device.type == "cuda" and torch.cuda.is_current_stream_capturing()):
+                m["armed"] = False
+
+    def _tracked_step(self):
+        """A step that keeps the marker is about to be issued: its restarts arm it.  Captured into a graph, it does so again on
+        every replay, whatever the host does in between."""
+        m = self._mark
+        if not m["graphs"]:
+            m["armed"] = True
+            if torch.cuda.is_current_stream_capturing():
+                m["graphs"] = True
+
+    def _arm(self):
+        """The cells or the pool were replaced: compare once, on the device.  One layout: every env that equals it is marked 0;
+        more: everything starts unknown, and the restarts mark the envs as they go."""
+        if not self._tracks() or self._pool[0].shape[0] != 1:
+            self._disarm()
+            return
+        same = (self._cells == self._pool[0][0]).flatten(1).all(dim=1)
+        self._marker.copy_(same.to(torch.int32) - 1)
+        self._mark["armed"] = True
+
+    def _restarted(self):
+        """reset_done() / reset() restarted the envs of `was_reset` from the pool: with one layout they ARE that layout now; with
+        more, their marker would name the layout they had before -- unknown."""
+        if self._tracks() and (self._mark["armed"] or self._pool[0].shape[0] == 1):
+            one = self._pool[0].shape[0] == 1
+            self._marker.masked_fill_(self.was_reset.bool(), 0 if one else -1)
+            if one:
+                self._mark["armed"] = True
+
+    @property
     def grid(self) -> torch.Tensor:
         """The grid as (type, color, state) bytes u8[B,H,W,3] ([y][x]: layouts.grid_from_product gives the reference's
         Grid.state) -- unpacked from `cells` on every access; for inspection, tests and checkpoints, not the hot path.  A box that
         holds something carries it in the upper bits of its state byte (include/mgx.h "BOX CONTENTS"; `& 3` is what Grid.state
         shows)."""
         if self.spec.cell_bytes == 3:
-            return self.cells
-        c = self.cells.to(torch.int32)
+            return self._cells
+        c = self._cells.to(torch.int32)
         if self.spec.cell_bytes == 1:                        # MgxCell8: joint (type, state) code | color << 4 | opaque << 7
             tc = c & 0xF
             door = (tc == 11) | (tc == 12)
@@ -282,7 +344,8 @@ class BatchedMultiGridEnv:
             if (an[..., 2] >= sp.width).any() or (an[..., 3] >= sp.height).any() or (an[..., 1] > 3).any():
                 raise ValueError("agent position / direction out of range")
         self._refuse_carried_contents(a)
-        self.cells.copy_(torch.from_numpy(layouts.pack_cells_for(sp, g.cpu().numpy())))
+        self._cells.copy_(torch.from_numpy(layouts.pack_cells_for(sp, g.cpu().numpy())))
+        self._arm()
         self.agents.copy_(a)
         if rng is not None:
             r = np.asarray(rng.cpu() if torch.is_tensor(rng) else rng)
@@ -360,13 +423,13 @@ class BatchedMultiGridEnv:
         self.join()
         if one_hot:
             if self.spec.cell_bytes == 1:          # compact cells: the one-hot STEP is one launch (round 6); the observation of a
-                self.backend.gen_obs(self.batch, self.cells, self.agents, self.obs, self.dir)      # reset is two: gen_obs, then
+                self.backend.gen_obs(self.batch, self._cells, self.agents, self.obs, self.dir)      # reset is two: gen_obs, then
                 self.backend.one_hot(self.obs, self._one_hot_buffer())                             # the one-hot kernel over it
                 return self._one_hot, self.dir
             self._need_wide_cells("one-hot output")
-            self.backend.gen_obs(self.batch, self.cells, self.agents, self._one_hot_buffer(), self.dir, one_hot=True)
+            self.backend.gen_obs(self.batch, self._cells, self.agents, self._one_hot_buffer(), self.dir, one_hot=True)
             return self._one_hot, self.dir
-        self.backend.gen_obs(self.batch, self.cells, self.agents, self.obs, self.dir)
+        self.backend.gen_obs(self.batch, self._cells, self.agents, self.obs, self.dir)
         return self.obs, self.dir
 
     def _one_hot_buffer(self):
@@ -411,18 +474,22 @@ class BatchedMultiGridEnv:
             self._need_state()
         if self._parent is not None:
             self._check_fresh()
-        if actions.dtype is not torch.int8 or actions.shape != self._act_shape or actions.device != self.cells.device \
+        if actions.dtype is not torch.int8 or actions.shape != self._act_shape or actions.device != self._cells.device \
                 or not actions.is_contiguous():
             raise ValueError(f"actions must be a contiguous int8 tensor of shape {tuple(self._act_shape)} "
-                             f"on {self.cells.device}")
+                             f"on {self._cells.device}")
         if sub_shards == 1 and hook_order is None and not self._chains_pending:      # the hot path: one dict lookup, one call
             fast = self._bound.get((auto_reset, one_hot))
             if fast is not None:
+                if fast[2]:
+                    self._tracked_step()
+                elif self._mark["armed"]:
+                    self._disarm()
                 fast[0](actions)
                 return fast[1]
         if hook_order is not None and (hook_order.dtype is not torch.uint8 or hook_order.shape != self._act_shape
-                                       or hook_order.device != self.cells.device or not hook_order.is_contiguous()):
-            raise ValueError(f"hook_order must be a contiguous uint8 tensor of shape {tuple(self._act_shape)} on {self.cells.device}")
+                                       or hook_order.device != self._cells.device or not hook_order.is_contiguous()):
+            raise ValueError(f"hook_order must be a contiguous uint8 tensor of shape {tuple(self._act_shape)} on {self._cells.device}")
         if one_hot and not (self.spec.cell_bytes == 1 and self.spec.env_kind == "empty"):
             self._need_wide_cells("one-hot output")        # (compact cells: the hook-free step has a one-hot instantiation, round 6)
         generate = bool(auto_reset) and getattr(self, "_gen", None) is not None
@@ -443,6 +510,11 @@ class BatchedMultiGridEnv:
         if fast is None:
             fast = self._bind_step(*key)
         out = (self._one_hot if one_hot else self.obs), self.dir, self.reward, self.terminated, self.truncated
+        tracked = fast is not False and getattr(fast, "tracked", False)
+        if tracked:
+            self._tracked_step()
+        else:                                   # (chains, one-hot, generated and plain steps, host launchers: the marker is not kept)
+            self._disarm()
         if fast is not False:
             if P > 1:
                 ev = self._fork_event
@@ -457,7 +529,7 @@ class BatchedMultiGridEnv:
                 self._chains_pending, self._chains_P = True, P
                 return out
             if isinstance(auto_reset, bool) and isinstance(one_hot, bool):
-                self._bound[(auto_reset or generate, one_hot)] = (fast, out)       # (the hot path's entry: cleared with _bound)
+                self._bound[(auto_reset or generate, one_hot)] = (fast, out, tracked)   # (the hot path's entry: cleared with _bound)
             fast(actions, hook_order)
             return out
         # launchers without bind_step (the test-suite's oracle backend)
@@ -471,7 +543,7 @@ class BatchedMultiGridEnv:
         if hook_order is not None:
             kw["hook_order"] = hook_order
         obs = self._one_hot_buffer() if one_hot else self.obs
-        self.backend.step(self.batch, self.cells, self.agents, self.rng, self.step_count, actions,
+        self.backend.step(self.batch, self._cells, self.agents, self.rng, self.step_count, actions,
                           self.aux if sp.env_kind != "empty" else None, self.err,
                           obs, self.dir, self.reward, self.terminated, self.truncated, **kw)
         if generate:
@@ -523,11 +595,15 @@ class BatchedMultiGridEnv:
                 self._fork_event = torch.cuda.Event()
                 self._fork_event.record(torch.cuda.current_stream(self.device))     # (creates the handle)
             head = (self.batch, parts, self._chain_streams[:parts])
-        f = bind(*head, self.cells, self.agents, self.rng, self.step_count,
+        # the step with auto-reset from a layout pool keeps the layout marker (mgx_step_tracked); every other form leaves it alone
+        # and step() takes the promise back before it runs
+        track = ar is not None and parts == 1 and not one_hot and not generate and self._tracks()
+        f = bind(*head, self._cells, self.agents, self.rng, self.step_count,
                  self.aux if self.spec.env_kind != "empty" else None, self.err,
                  self._one_hot_buffer() if one_hot else self.obs, self.dir, self.reward, self.terminated, self.truncated,
                  auto_reset=ar, one_hot=one_hot,
-                 **({"generate": (self._gen, self.episode, self.was_reset)} if generate else {}))
+                 **({"generate": (self._gen, self.episode, self.was_reset)} if generate else {}),
+                 **({"marker": self._marker} if track else {}))
         self._bound[key] = f
         return f
 
@@ -556,8 +632,9 @@ class BatchedMultiGridEnv:
                 continue
             c = object.__new__(BatchedMultiGridEnv)
             c.spec, c.batch, c.first_env, c.device, c.backend = self.spec, hi - lo, self.first_env + lo, self.device, self.backend
-            for name in ("cells", "agents", "rng", "step_count", "aux", "obs", "dir", "reward", "terminated", "truncated"):
+            for name in ("_cells", "agents", "rng", "step_count", "aux", "obs", "dir", "reward", "terminated", "truncated"):
                 setattr(c, name, getattr(self, name)[lo:hi])
+            c._marker, c._mark = self._marker[lo:hi], self._mark          # (its slice of the layout marker; one host flag for all)
             c.err = self.err                                                  # (shared: the kernels update it atomically)
             c._loaded, c._act_shape, c._bound = True, torch.Size((hi - lo, self.spec.num_agents)), {}
             c._parent, c._made_version, c._layout_version = self, self._layout_version, 0
@@ -633,7 +710,10 @@ class BatchedMultiGridEnv:
                 for s in others:                                             # join
                     side.wait_stream(s)
         stream.wait_stream(side)
-        return StepGraph(self, graph, len(shards), (shards, others, actions, hook_order))
+        sg = StepGraph(self, graph, len(shards), (shards, others, actions, hook_order))
+        ent = shards[0]._bound.get((bool(auto_reset), bool(one_hot)))
+        sg._tracked = bool(ent and ent[2])       # (its steps keep the layout marker; otherwise a replay takes the promise back first)
+        return sg
 
     def rollout(self, actions: torch.Tensor, out: dict | None = None, auto_reset: bool = False, one_hot: bool = False) -> dict:
         """`T` consecutive `step`s in one kernel launch (env state stays in LDS between steps); bit-identical to
@@ -651,10 +731,11 @@ class BatchedMultiGridEnv:
         if not (self.spec.cell_bytes == 1 and self.spec.env_kind == "empty" and not one_hot and not generate):
             self._need_wide_cells("rollout (the steps of one launch)")      # (compact cells: the hook-free rollout, round 6)
         self.join()
+        self._disarm()                          # (the rollout kernels write the grids back without keeping the layout marker)
         sp, B = self.spec, self.batch
         if actions.dtype != torch.int8 or actions.dim() != 3 or tuple(actions.shape[1:]) != (B, sp.num_agents) \
-                or actions.device != self.cells.device or not actions.is_contiguous():
-            raise ValueError(f"actions must be a contiguous int8 tensor of shape (T, {B}, {sp.num_agents}) on {self.cells.device}")
+                or actions.device != self._cells.device or not actions.is_contiguous():
+            raise ValueError(f"actions must be a contiguous int8 tensor of shape (T, {B}, {sp.num_agents}) on {self._cells.device}")
         T, A, v, dev = actions.shape[0], sp.num_agents, sp.view_size, self.device
         if out is None:
             out = {"obs": torch.empty((T, B, A, v, v, 21 if one_hot else 3), dtype=torch.uint8, device=dev),
@@ -666,13 +747,13 @@ class BatchedMultiGridEnv:
             out["was_reset"] = torch.empty((T, B), dtype=torch.uint8, device=dev)
         generate = bool(auto_reset) and getattr(self, "_gen", None) is not None
         if generate:        # episode starts generated on the device: the envs whose episode ends with step t are regenerated
-            self.backend.rollout(B, T, self.cells, self.agents, self.rng, self.step_count, actions,          # right after it
+            self.backend.rollout(B, T, self._cells, self.agents, self.rng, self.step_count, actions,          # right after it
                                  self.aux if sp.env_kind != "empty" else None, self.err, out["obs"], out["dir"],
                                  out["reward"], out["terminated"], out["truncated"],
                                  generate=(self._gen, self.episode, out["was_reset"]), **({"one_hot": True} if one_hot else {}))
             return out
         ar = self._auto_reset_args(auto_reset, out.get("was_reset"))
-        self.backend.rollout(B, T, self.cells, self.agents, self.rng, self.step_count, actions,
+        self.backend.rollout(B, T, self._cells, self.agents, self.rng, self.step_count, actions,
                              self.aux if sp.env_kind != "empty" else None, self.err, out["obs"], out["dir"],
                              out["reward"], out["terminated"], out["truncated"],
                              **({"auto_reset": ar} if ar is not None else {}), **({"one_hot": True} if one_hot else {}))
@@ -694,7 +775,7 @@ class BatchedMultiGridEnv:
             self._full = torch.zeros((self.batch, self.spec.width, self.spec.height, 3), dtype=torch.uint8,
                                      device=self.device)
         try:
-            self.backend.full_obs(self.batch, self.cells, self.agents, self._full)
+            self.backend.full_obs(self.batch, self._cells, self.agents, self._full)
         except _lib.MgxError as e:
             # mgx_full_obs stages one env's cells and output in 64 KiB of LDS: (cb + 3) * W * H + 96 bytes, which refuses sides
             # beyond 114 / 127 / 104 on 16-bit / compact / byte cells where the step runs up to 255.  Those
@@ -723,7 +804,7 @@ class BatchedMultiGridEnv:
         ts = int(tile_size)
         if not 1 <= ts <= 64:
             raise ValueError(f"render: tile_size must be in 1..64, got {tile_size}")
-        cells, agents = self.cells, self.agents
+        cells, agents = self._cells, self.agents
         if env_ids is not None:
             ids = torch.as_tensor(env_ids)
             if ids.dtype.is_floating_point or ids.dtype.is_complex or ids.dtype == torch.bool:
@@ -785,6 +866,7 @@ class BatchedMultiGridEnv:
             if t is not None:
                 old[2].copy_(t)
             self.episode.zero_(); self.was_reset.zero_()
+            self._arm()                  # (the layout marker spoke of the old layouts)
             return
         self._gen = None
         self._pool = (cells.to(self.device).contiguous(), a.to(self.device).contiguous(), t)
@@ -792,6 +874,7 @@ class BatchedMultiGridEnv:
         self.was_reset = torch.zeros((self.batch,), dtype=torch.uint8, device=self.device)
         self._bound.clear()              # (the pre-bound launchers hold the old pool's pointers ...
         self._layout_version += 1        #  ... and so do sub-shards and captured graphs made before: they now refuse to run)
+        self._arm()
 
     def set_layout_generator(self, kind: str, layout_seed: int = 0, *, room_size: int = 0, start=(1, 1, 0),
                              max_hallway_keys: int = 1, max_keys_per_room: int = 2, staged=True, lead: int | None = None):
@@ -898,6 +981,7 @@ class BatchedMultiGridEnv:
                                   "agents": torch.zeros((B, sp.num_agents, 8), dtype=torch.uint8, device=dev),
                                   "aux": torch.zeros((B, 16), dtype=torch.uint8, device=dev) if sp.env_kind != "empty" else None,
                                   "words": torch.zeros((B, 12), dtype=torch.int64, device=dev), "tag": tag, "phase": [0]}
+        self._disarm()                   # (no pool: nothing keeps the layout marker any more)
         self._pool = None
         self.episode = torch.zeros((self.batch,), dtype=torch.int32, device=self.device)
         self.was_reset = torch.zeros((self.batch,), dtype=torch.uint8, device=self.device)
@@ -912,13 +996,14 @@ class BatchedMultiGridEnv:
         self._need_state()
         self.join()
         if getattr(self, "_gen", None) is not None:
-            self.backend.reset_generate(self.batch, self._gen, self.cells, self.agents, self.rng, self.step_count,
+            self.backend.reset_generate(self.batch, self._gen, self._cells, self.agents, self.rng, self.step_count,
                                         self.aux if self.spec.env_kind != "empty" else None, self.episode, self.was_reset)
             return self.was_reset
         if getattr(self, "_pool", None) is None:
             raise RuntimeError("call set_layout_pool() or set_layout_generator() first")
-        self.backend.reset_done(self.batch, self.first_env, self._pool, self.cells, self.agents, self.step_count,
+        self.backend.reset_done(self.batch, self.first_env, self._pool, self._cells, self.agents, self.step_count,
                                 self.aux, self.episode, self.was_reset)
+        self._restarted()
         return self.was_reset
 
     def reset(self, seed: int | None = None, mask: torch.Tensor | None = None, one_hot: bool = False):
@@ -946,8 +1031,8 @@ class BatchedMultiGridEnv:
         if mask is not None:
             self._need_state()
             if not torch.is_tensor(mask) or mask.dtype not in (torch.bool, torch.uint8) or tuple(mask.shape) != (self.batch,) \
-                    or mask.device != self.cells.device or not mask.is_contiguous():
-                raise ValueError(f"mask must be a contiguous bool or uint8 tensor of shape ({self.batch},) on {self.cells.device}")
+                    or mask.device != self._cells.device or not mask.is_contiguous():
+                raise ValueError(f"mask must be a contiguous bool or uint8 tensor of shape ({self.batch},) on {self._cells.device}")
             sel = mask.view(torch.uint8) if mask.dtype is torch.bool else mask
         if seed is None and not self._loaded and not self._seeded:
             raise ValueError("reset(): np_random has never been seeded (all-zero PCG64 words are not a generator): pass seed=, or "
@@ -962,11 +1047,12 @@ class BatchedMultiGridEnv:
             side = (gen.get("stage") or {}).get("stream")
             if side is not None:                 # (generator launches beside the steps read gen_state / rng: behind them)
                 torch.cuda.current_stream(self.device).wait_stream(side)
-            self.backend.reset_generate_select(self.batch, gen, sel, words, self.cells, self.agents, self.rng, self.step_count,
+            self.backend.reset_generate_select(self.batch, gen, sel, words, self._cells, self.agents, self.rng, self.step_count,
                                                aux, self.episode, self.was_reset)
         else:
-            self.backend.reset_select(self.batch, self.first_env, pool, sel, words, self.cells, self.agents, self.rng,
+            self.backend.reset_select(self.batch, self.first_env, pool, sel, words, self._cells, self.agents, self.rng,
                                       self.step_count, self.aux, self.episode, self.was_reset)
+            self._restarted()
         if seed is not None:
             self._seeded = True
         self._loaded = True

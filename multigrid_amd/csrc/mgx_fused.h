@@ -81,6 +81,7 @@ struct KernelArgs {
     int32_t dbg;        // debug: bit p set = skip phase p (profiling only, mgx_debug_skip_phases)
     int32_t flags;      // bit 0: the grid does not fit the Infinity Cache -- launch the STREAM instantiation (nt tile loads)
                         // bit 1: few wavefronts (latency regime) -- launch the DMA instantiation (LDS-DMA tile loads)
+                        // bit 2: P0 reads grid_layout (below) and skips the tile load of wavefronts still on one pool layout
     int32_t T;          // steps per launch (mgx_rollout), 1 otherwise
     // per-wavefront LDS slice: its stride and the slot count its carve is derived from (LdsCarve below)
     int32_t wave_lds;
@@ -112,6 +113,9 @@ struct KernelArgs {
                         // format cannot hold, [1] += outer-ring cells that are not WALL (what mgx_pack_grid_env reports)
     int32_t *bounds;    // -DMGX_BOUNDS_CHECK=1 builds: [0] += LDS accesses outside the wavefront's slice, [1] = last site id
     int32_t span_base;  // -DMGX_TIMESTAMPS=1 builds: first record of this launch in g_span (tools/span_probe.py, tools/chain_overlap.py)
+    int32_t *grid_layout;   // mgx_step_tracked (include/mgx.h): i32[B] or null -- k >= 0: env b's grid equals pool_grid[k], -1: unknown.
+                            // The one-step kernels with the fused auto-reset MAINTAIN it (a restart stores k, a cell written back
+                            // stores -1); P0 READS it only where the host set flags bit 2 (plan_marker_read, mgx_kernels.hip)
 };
 
 // -DMGX_DEBUG_KNOBS=1 (the tools' build, `python -m multigrid_amd.build --debug-knobs` -> lib/libmgx_dbg.so): phase

@@ -19,6 +19,12 @@
         if constexpr (PERSIST) __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(val), make_rsrc((base), (n)), (idx), 0, 16); \
         else (base)[idx] = (uint8_t)(val);                                                                           \
     } while (0)
+    // MARK: the one-step kernels with the fused auto-reset keep the per-env layout marker of mgx_step_tracked (include/mgx.h,
+    // KernelArgs::grid_layout) when the launch has one: a restart stores the layout's index, a cell written back to the grid stores
+    // -1.  MARK_RD: the throughput family also READS it in P0 where the host asks for it (a.flags bit 2) -- a runtime, wave-uniform
+    // branch inside the existing instantiations, none of its own
+    constexpr bool MARK = AR && MODE == 1 && !GEN && !C8 && !B3;
+    constexpr bool MARK_RD = MARK && !DMA;
     constexpr int V2 = V * V;
     constexpr int NW = (V2 + 63) / 64;          // 64-bit mask words per view = lane passes per view
     constexpr int CB = C8 ? 1 : kCellBytes;      // bytes per grid cell: MgxCell, or the compact MgxCell8 (include/mgx.h)
@@ -76,8 +82,10 @@
         const uint8_t *e_trunc = DO_STEP ? a.truncated : nullptr;      // (its kernarg line holds the output pointers MGX_LATE asks for later)
         const uint64_t *e_gs = GEN ? a.gen.gen_state : nullptr;       // (GEN: the generator's and the staging slots' lines)
         const int32_t *e_tag = GEN ? a.gen.stage.tag : nullptr;
+        const int32_t *e_lay = MARK_RD ? a.grid_layout : nullptr;     // (MARK_RD: the marker and the pool, for P0's first load)
+        const uint8_t *e_pool = MARK_RD ? a.pool_grid : nullptr;
         asm volatile("" :: "s"(e_batch), "s"(e_grid), "s"(e_agents), "s"(e_rng), "s"(e_sc), "s"(e_act), "s"(e_hord), "s"(e_aux),
-                     "s"(e_bd), "s"(e_ep), "s"(e_trunc), "s"(e_gs), "s"(e_tag));
+                     "s"(e_bd), "s"(e_ep), "s"(e_trunc), "s"(e_gs), "s"(e_tag), "s"(e_lay), "s"(e_pool));
     }
     // SHAPE != 0: an instantiation for ONE (W, H, A, envs per wavefront) of mgx_fused.h's kShapes -- the latency family's answer to
     // what a lone wavefront pays for a runtime shape: every LDS offset of the carve, the agent loops, the row pitch and the
@@ -265,11 +273,21 @@
     const __amdgpu_buffer_rsrc_t grsrc = make_rsrc(gsrc, grec);
     const int lane16 = 16 * lane;
     const int env_of_lane = (lane * inv_A_) >> 16, agent_of_lane = lane - env_of_lane * A;   // slot `lane` = (env, agent)
+    // (0) MARK_RD launches that read the layout marker (a.flags bit 2): env `lane`'s marker goes out FIRST, so that it can be waited
+    // for alone -- vmcnt counts in order -- while the small inputs below stay in flight across the branch it decides
+    [[maybe_unused]] const bool read_marker = MARK_RD && (a.flags & 4) != 0;                    // wave-uniform
+    [[maybe_unused]] int32_t in_lay = -1;
+    if constexpr (MARK_RD) {
+        if (read_marker) in_lay = (int32_t)__builtin_amdgcn_raw_buffer_load_b32(make_rsrc(a.grid_layout + e0, Gc * 4), lane * 4, 0, 0);
+    }
     // (1) what the draws (P1a) need goes out first: this lane's env's PCG64 words and its agent's jump-ahead constants
     u32x4 in_rngA = {0, 0, 0, 0}, in_rngB = {0, 0, 0, 0};                    // (ROLL: two envs' halves, copied to LDS)
     u32x4 in_jmpA = {0, 0, 0, 0}, in_jmpB = {0, 0, 0, 0};
-    if (DO_STEP && A > 1) {
-        const __amdgpu_buffer_rsrc_t rr = make_rsrc(a.rng + e0 * 4, Gc * 32);
+    // (MARK_RD kernels issue these loads whatever A is -- for one agent through a descriptor of no bytes --: the wait for the marker
+    // then counts them exactly and leaves them in flight, and a launch that does not read the marker waits for nothing; under a
+    // runtime condition the wait-count pass makes every launch wait for them in front of the tile burst)
+    if (MARK_RD || (DO_STEP && A > 1)) {
+        const __amdgpu_buffer_rsrc_t rr = make_rsrc(a.rng + e0 * 4, (MARK_RD && A <= 1) ? 0 : Gc * 32);
         if (ROLL) {                                                              // env-major copy: lane l holds words 2l, 2l+1
             in_rngA = __builtin_amdgcn_raw_buffer_load_b128(rr, lane16, 0,kInAux);
             for (int t = lane; t < A * 4; t += 64) jump[t] = kJump.w[1][t];          // constants for k = 1..A, re-read every step
@@ -322,7 +340,39 @@
         _Pragma("unroll") for (int u = 0; u < U; ++u)                                                                 \
             dst[u] = __builtin_amdgcn_raw_buffer_load_b128(grsrc, lane16 + 1024 * (u & 3), (base) + 4096 * (u >> 2), kTileAux); \
     }
-    if constexpr (!B3 && PITCH == 0) { MGX_TILE_BURST(tv, 0) }     // (PITCH: the tile is laid out cell by cell, below)
+    // MARK_RD: a wavefront whose envs ALL sit on the same pool layout k (their grids in device memory equal pool_grid[k] bit for
+    // bit: the marker's promise) takes the layout instead of its envs' grids -- the host asks for the marker only where an env's
+    // grid is a power of two of at most 1 KiB (plan_marker_read), so every 16-byte vector of the wavefront's tile is the layout's
+    // vector at (16 lane) mod HWB, whichever round of the burst it belongs to: ONE load from a cache-resident line fills them all.
+    // The burst itself stays the straight line it is, on both paths (a branch around two forms of it made the wait-count pass
+    // drain half the tile in front of the draws below: vmcnt(4) where the straight line has vmcnt(12)): its first load goes
+    // through `rs0` -- the grid or the layout --, the other seven through `rs1` -- the grid or a descriptor of NO bytes, whose
+    // loads return zeros without touching memory.
+    [[maybe_unused]] bool pristine = false;                                  // wave-uniform
+    [[maybe_unused]] __amdgpu_buffer_rsrc_t rs0 = grsrc, rs1 = grsrc;
+    [[maybe_unused]] int lane16_0 = lane16;
+    if constexpr (MARK_RD) {
+        // (everything that depends on the marker stays INSIDE this branch: a launch that does not read it must not wait for
+        // anything in front of its burst)
+        if (read_marker) {
+            const int32_t k0 = __builtin_amdgcn_readfirstlane(in_lay);
+            pristine = k0 >= 0 && __builtin_amdgcn_ballot_w64(lane < Gc && in_lay != k0) == 0;
+            if (pristine) {
+                rs0 = make_rsrc(a.pool_grid + (int64_t)k0 * HWB, HWB);
+                rs1 = make_rsrc(gsrc, 0);
+                lane16_0 = lane16 & (HWB - 1);
+            }
+        }
+    }
+    if constexpr (!B3 && PITCH == 0) {                              // (PITCH: the tile is laid out cell by cell, below)
+        if constexpr (MARK_RD) {
+            tv[0] = __builtin_amdgcn_raw_buffer_load_b128(rs0, lane16_0, 0, kTileAux);
+            _Pragma("unroll") for (int u = 1; u < U; ++u)
+                tv[u] = __builtin_amdgcn_raw_buffer_load_b128(rs1, lane16 + 1024 * (u & 3), 4096 * (u >> 2), kTileAux);
+        } else {
+            MGX_TILE_BURST(tv, 0)
+        }
+    }
     // B3 (byte grids): the first 16 rows of 256 cells -- a C4 wavefront's whole tile -- are requested HERE, with the other formats'
     // tile burst, and converted below once the small inputs are in LDS (round 5's first form issued them after that wait: two
     // memory round trips in a row).  One 12-byte load per lane = 4 cells: a load instruction covers 768 contiguous bytes.
@@ -505,12 +555,21 @@
         }
     } else
     if constexpr (!DMA && PITCH == 0) {
+        if (MARK_RD && pristine) {              // the one layout vector, into every env's tile (behind the wait: no wait count differs)
 #pragma unroll
-        for (int u = 0; u < U; ++u)
-            if (lane16 + 1024 * u < len) {
-                MGX_CHECK_LDS_PTR(1, tile_raw + lane16 + 1024 * u, 16);
-                *reinterpret_cast<u32x4 *>(tile_raw + lane16 + 1024 * u) = tv[u];
-            }
+            for (int u = 0; u < U; ++u)
+                if (lane16 + 1024 * u < len) {
+                    MGX_CHECK_LDS_PTR(1, tile_raw + lane16 + 1024 * u, 16);
+                    *reinterpret_cast<u32x4 *>(tile_raw + lane16 + 1024 * u) = tv[0];
+                }
+        } else {
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (lane16 + 1024 * u < len) {
+                    MGX_CHECK_LDS_PTR(1, tile_raw + lane16 + 1024 * u, 16);
+                    *reinterpret_cast<u32x4 *>(tile_raw + lane16 + 1024 * u) = tv[u];
+                }
+        }
     }
     if (big_tile && !B3) {
         if constexpr (!DMA) {
@@ -786,6 +845,10 @@
                 const int lay = (int)__builtin_amdgcn_readlane(my_lay, e);
                 wave_sync();
                 if (lane == 0) p_ep[b] = ep + 1;
+                if constexpr (MARK) {                                            // the env's grid IS layout `lay` from here on (the copy
+                    int32_t *const p_lay = MGX_LATE(grid_layout);                // below); a cell written later in this step stores -1
+                    if (p_lay && lane == 0) p_lay[b] = lay;                      // behind it, in program order
+                }
                 const uint8_t *sg = MGX_LATE(pool_grid) + (int64_t)lay * HWG;
                 uint8_t *etile = tile + e * TSB;
                 uint8_t *gg = MGX_LATE(grid) + b * HWG;
@@ -974,6 +1037,10 @@
                 if (!ROLL) {                                                     // ROLL writes the whole tile back at the end
                     if constexpr (B3) store_obs_cell(MGX_LATE(grid) + (e0 + env_of_lane) * (int64_t)HWG + (ev.off >> 1) * 3, ev.ncell);
                     else store_cell(CB, MGX_LATE(grid) + (e0 + env_of_lane) * HWB + ev.off, ev.ncell);
+                    if constexpr (MARK) {                                        // the env has left its pool layout
+                        int32_t *const p_lay = MGX_LATE(grid_layout);
+                        if (p_lay) p_lay[e0 + env_of_lane] = -1;
+                    }
                 }
             }
         }
@@ -1002,11 +1069,13 @@
                 const int64_t b = e0 + e;
                 uint8_t *etile = tile + e * TSB;
                 uint8_t *ggrid = MGX_LATE(grid) + b * HWG;
+                [[maybe_unused]] int32_t *const p_lay = MARK ? MGX_LATE(grid_layout) : nullptr;
                 auto dirty = [=](int off) {
                     if constexpr (B3) store_obs_cell(ggrid + (off >> 1) * 3, cell_unpack_full(load_cell16(etile + off)));
                     else if (!ROLL) store_cell_raw(CB, ggrid + off, load_cell_raw(CB, etile + off));
+                    if constexpr (MARK) { if (p_lay) p_lay[b] = -1; }            // (the layout marker: this env has left its pool layout)
                 };
-                int k0 = 0;                                                      // the agents below the cutoff have committed already
+                int k0 = 0;                                                     // the agents below the cutoff have committed already
                 if constexpr (PREFIX) { if (A > 1) while (k0 < A && (ord[e * A + k0] & 0x80)) ++k0; }
                 else k0 = (A > 1 && (ord[e * A] & 0x80)) ? 1 : 0;
                 const int rc = handle_actions(cf, etile, rows + e * A, acts + e * A, ord + e * A, rew + e * A,
@@ -1035,6 +1104,10 @@
             auto dirty = [=](int off) {
                 if constexpr (B3) store_obs_cell(ggrid + (off >> 1) * 3, cell_unpack_full(load_cell16(etile + off)));
                 else if (!ROLL) store_cell_raw(CB, ggrid + off, load_cell_raw(CB, etile + off));
+                if constexpr (MARK) {                                            // (the layout marker: as in P1c.  No hook writes a cell
+                    int32_t *const p_lay = MGX_LATE(grid_layout);                // today: the load is only made where one does)
+                    if (p_lay) p_lay[b] = -1;
+                }
             };
             uint8_t *eaux = reinterpret_cast<uint8_t *>(auxl + e);
             post_step_hook(cf, env_kind, etile, rows + e * A, acts + e * A, eaux, sc, rew + e * A, dirty, p_hord ? ord + e * A : nullptr);

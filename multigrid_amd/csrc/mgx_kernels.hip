@@ -269,6 +269,24 @@ void bind_auto_reset(KernelArgs &ka, const MgxSpec *spec, const MgxAutoReset &ar
     if (occupancy && !ka.pool_grid) ka.pool_grid = reinterpret_cast<const uint8_t *>(spec);
 }
 
+// The layout marker of mgx_step_tracked (include/mgx.h): every one-step launch with the fused auto-reset that gets the pointer
+// MAINTAINS it; whether P0 also READS it is decided here, per launch (ka.flags bit 2):
+//   the throughput family only (no LDS-DMA instantiation, more than 2048 wavefronts) -- a lone wavefront of the latency family
+//     would pay a dependent round trip in front of its tile loads for nothing (C2's whole step is 5.3 us);
+//   a pool of ONE layout -- with more, consecutive envs sit on consecutive layouts ((first_env + b + 7919 episode) mod K) and no
+//     wavefront's envs would agree on one;
+//   an env's grid a power of two of at most 1 KiB -- the wavefront's 16-byte vectors then all fall on the one vector of the
+//     layout that lane's offset modulo the grid names, whatever the round of the burst: ONE load replaces them all.
+void plan_marker_read(LaunchPlan &lp, const MgxAutoReset &ar, int32_t *grid_layout) {
+    KernelArgs &ka = lp.ka;
+    ka.grid_layout = grid_layout;
+    const int hwb = ka.sp.width * ka.sp.height * cell_bytes_of(ka.sp);
+    // (... and the wavefront's tile one burst of 8 KiB at most, which the envs-per-wavefront choice gives such grids anyway)
+    if (!(ka.flags & 2) && lp.wavefronts() > 2048 && ar.pool_size == 1 && hwb >= 16 && hwb <= 1024 && (hwb & (hwb - 1)) == 0
+        && ka.Gw * hwb <= 8192 && !misaligned(ar.pool_grid, 16))
+        ka.flags |= 4;
+}
+
 // Staged generation (include/mgx.h: MgxGenStage), for the generated step and mgx_stage_generate: the slots are there (and A > 1) ...
 bool stage_present(const MgxSpec &sp, const MgxGenStage &st) {
     return st.grid && st.agents && st.words && st.tag && (st.aux || sp.env_kind == MGX_KIND_EMPTY) && sp.num_agents > 1;
@@ -534,7 +552,9 @@ int mgx_gen_obs_one_hot(const MgxSpec *spec, int64_t batch, const MgxCell *grid,
 }
 
 // The one implementation behind every step entry point (include/mgx.h: MgxStepArgs).  `occupancy`: query only (mgx_sub_shards).
-static int step_common(const MgxSpec *spec, int64_t batch, const MgxStepArgs &sa, void *stream, int *occupancy = nullptr) {
+// `grid_layout`: the per-env layout marker of mgx_step_tracked, or null.
+static int step_common(const MgxSpec *spec, int64_t batch, const MgxStepArgs &sa, void *stream, int *occupancy = nullptr,
+                       int32_t *grid_layout = nullptr) {
     const bool roll = sa.steps != 1, one_hot = sa.one_hot != 0;
     const MgxAutoReset *ar = sa.auto_reset;
     const MgxLayoutGen *gen = sa.generate;
@@ -559,6 +579,11 @@ static int step_common(const MgxSpec *spec, int64_t batch, const MgxStepArgs &sa
     ka.grid_bad = spec->cell_bytes == 3 ? sa.grid_bad : nullptr;
     if (misaligned(ka.grid_bad, 4)) return MGX_ERR_INVALID_ARGUMENT;
     ka.T = roll ? sa.steps : 1;
+    if (grid_layout) {
+        if (!ar || roll || gen || cell_bytes_of(*spec) != kCellBytes || spec->cell_bytes == 3) return MGX_ERR_UNSUPPORTED;
+        if (misaligned(grid_layout, 4)) return MGX_ERR_INVALID_ARGUMENT;
+        plan_marker_read(lp, *ar, grid_layout);
+    }
     if (gen) {
         if (ar) return MGX_ERR_INVALID_ARGUMENT;
         if (spec->cell_bytes == 1 || spec->cell_bytes == 3) return MGX_ERR_UNSUPPORTED;        // (device-side generation writes 16-bit cells)
@@ -637,6 +662,11 @@ static MgxStepArgs step_args(MgxCell *grid, uint8_t *agents, uint64_t *rng, int3
 int mgx_step_ex(const MgxSpec *spec, int64_t batch, const MgxStepArgs *args, void *stream) {
     if (!args) return MGX_ERR_INVALID_ARGUMENT;
     return step_common(spec, batch, *args, stream);
+}
+
+int mgx_step_tracked(const MgxSpec *spec, int64_t batch, const MgxStepArgs *args, int32_t *grid_layout, void *stream) {
+    if (!args) return MGX_ERR_INVALID_ARGUMENT;
+    return step_common(spec, batch, *args, stream, nullptr, grid_layout);
 }
 
 int mgx_step(const MgxSpec *spec, int64_t batch, MgxCell *grid, uint8_t *agents, uint64_t *rng,

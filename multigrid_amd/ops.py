@@ -210,15 +210,25 @@ class HipBackend:
         return self._grid_bad
 
     def bind_step(self, B, grid, agents, rng, step_count, target, err, obs, dirs, reward, terminated, truncated,
-                  auto_reset=None, one_hot: bool = False, generate=None):
+                  auto_reset=None, one_hot: bool = False, generate=None, marker=None):
         """Pre-bound launcher for a policy-in-the-loop caller: every pointer except `actions` (and the optional `hook_order`)
         is resolved once into one MgxStepArgs, so a call costs one 4-argument ctypes transition (mgx_step_ex) + the kernel
         launch.  The tensors must stay alive and in place (they are the env's own buffers).  Returns f(actions, hook_order=None)
-        enqueuing one step on torch's current stream."""
-        fn = _lib.lib().mgx_step_ex
+        enqueuing one step on torch's current stream.
+        `marker`: the env's layout marker i32[B] (include/mgx.h: mgx_step_tracked) -- the step then keeps it and, where the
+        launch reads it, skips the grid load of envs still on their pool layout; `.tracked` of the result says whether it does."""
         sa, keep = self.step_args(grid, agents, rng, step_count, target, err, obs, dirs, reward, terminated, truncated,
                                   auto_reset, one_hot, generate)
         spec_ref, args_ref = C.byref(self.sc), C.byref(sa)
+        # (a library loaded through MGX_LIBMGX for an A/B may be older than the entry: it steps untracked -- _lib.lib())
+        tracked = marker is not None and hasattr(_lib.lib(), "mgx_step_tracked")
+        if tracked:
+            tracked_fn, marker_ptr = _lib.lib().mgx_step_tracked, marker.data_ptr()
+
+            def fn(spec_ref, B, args_ref, stream):
+                return tracked_fn(spec_ref, B, args_ref, marker_ptr, stream)
+        else:
+            fn = _lib.lib().mgx_step_ex
         dev, index = grid.device, grid.device.index
         device_ctx = torch.cuda.device
 
@@ -257,7 +267,8 @@ class HipBackend:
                 if rc:
                     _lib.check(rc, "mgx_stage_generate")
                 stage["launches"] = stage.get("launches", 0) + 1
-        step._keep = (sa, keep)
+        step._keep = (sa, keep, marker)
+        step.tracked = tracked
         return step
 
     def stage_generate(self, B, gen, rng, episode):
