@@ -671,6 +671,72 @@ int mgx_render_atlas(int32_t tile_size, uint8_t *atlas, void *stream);
 int mgx_render(const MgxSpec *spec, int64_t n, const MgxCell *grid, const uint8_t *agents, const uint8_t *obs, const uint8_t *atlas,
                int32_t tile_size, uint8_t *frames, void *stream);
 
+/* EPISODE ACCOUNTING (additive to ABI 11): the return, the length and the outcome of every episode, kept on the device beside the
+ * envs -- what a consumer of the reference's step() return values adds up from `rewards`, `terminations` and `truncations`
+ * (multigrid/base.py:338-340) and logs when an episode ends.  Build-defined like the auto-reset it follows: the reference has no
+ * batching and leaves the bookkeeping to its caller.
+ *
+ * State, per env b, all zero at creation (MgxEpisodeStats; every pointer required):
+ *   cur_return f64[B,A], cur_length i32[B]    the running episode
+ *   over u8[B]                                the episode has been closed and the env has not been restarted since
+ *   last_return f64[B,A], last_length i32[B]  the episode closed last
+ *   sum_return f64[B,A], sum_length i64[B]    over all closed episodes
+ *   counts i32[B,4]                           closed, terminated, rewarded, aborted
+ *
+ * mgx_episode_stats applies the outputs of `steps` consecutive steps -- reward f64[steps,B,A], terminated u8[steps,B,A], truncated
+ * u8[steps,B], was_reset u8[steps,B] (required unless restart == MGX_RESTART_NONE, then ignored) -- to it, for every env and step in
+ * step order:
+ *   1. restart == MGX_RESTART_BEFORE and was_reset[b]: the env was restarted before this step (mgx_step_autoreset: "restarted
+ *      before each step") -- the RESTART CLAUSE below.
+ *   2. not over[b]:  cur_return[b,a] += reward[b,a] (one f64 add per agent and step);  cur_length[b] += 1;
+ *      ended = truncated[b] != 0 || every terminated[b,a] != 0.  If ended the episode is CLOSED: last_* = cur_*;  sum_return[b,a] +=
+ *      cur_return[b,a] (one f64 add per agent and close);  sum_length += cur_length;  closed++;  terminated++ if every agent was
+ *      terminated;  rewarded++ if any cur_return[b,a] > 0;  cur_* = 0;  over[b] = 1.
+ *   3. over[b] (as step 1 left it): a step past the end -- nothing is accumulated.
+ *   4. restart == MGX_RESTART_AFTER and was_reset[b]: the env was regenerated after this step (mgx_step_generate) -- the restart
+ *      clause.
+ *   RESTART CLAUSE: if not over[b] and cur_length[b] > 0 the running episode is discarded (aborted++, cur_* = 0); over[b] = 0.
+ * mgx_episode_restart applies the restart clause alone to the envs of `select` (u8[B], non-zero = chosen; NULL = every env): what
+ * follows mgx_reset_done / mgx_reset_generate (select = their was_reset) and mgx_reset_select / mgx_reset_generate_select.
+ *
+ * `ended` is read from the step's OUTPUTS, the restart from the engine's own was_reset.  For every env kind but one the two agree
+ * with is_done() (multigrid/base.py:534-539); LockedHallwayEnv.step reports every agent terminated once all doors are unlocked
+ * without touching the agents' state (multigrid/envs/locked_hallway.py:222-225), so the engine lets such an env run on to its
+ * truncation: the episode closes where the outputs say so, the steps up to the engine's restart are steps past the end, and the
+ * restart opens the next episode.  Under auto-reset alone `aborted` therefore stays 0 for every env kind.
+ *
+ * MgxEpisodeTrace (may be NULL, and so may each of its pointers): closed u8[steps,B], episode_return f64[steps,B,A],
+ * episode_length i32[steps,B], written for EVERY (step, env): the closed episode's values at a closing step, zeros elsewhere.
+ *
+ * Every env's arithmetic is its own, in step order, without atomics: bit for bit what a sequential model computes.
+ * Return codes: a bad spec (NULL, num_agents outside 1..MGX_MAX_AGENTS), batch < 0, steps < 0, an unknown `restart`:
+ * MGX_ERR_INVALID_ARGUMENT; then batch == 0 or steps == 0: MGX_OK, nothing is launched; then a missing required pointer or a
+ * misaligned one (8 bytes for f64 / i64, 4 for i32): MGX_ERR_INVALID_ARGUMENT; more than INT_MAX wavefronts (one per 64 /
+ * num_agents envs; the restart: one per 64 envs): MGX_ERR_UNSUPPORTED.  The grid's cell format plays no part. */
+typedef struct MgxEpisodeStats {
+    double *cur_return;
+    int32_t *cur_length;
+    uint8_t *over;
+    double *last_return;
+    int32_t *last_length;
+    double *sum_return;
+    int64_t *sum_length;
+    int32_t *counts;
+} MgxEpisodeStats;
+
+typedef struct MgxEpisodeTrace {
+    uint8_t *closed;
+    double *episode_return;
+    int32_t *episode_length;
+} MgxEpisodeTrace;
+
+enum { MGX_RESTART_NONE = 0, MGX_RESTART_BEFORE = 1, MGX_RESTART_AFTER = 2 };
+
+int mgx_episode_stats(const MgxSpec *spec, int64_t batch, int32_t steps, const double *reward, const uint8_t *terminated,
+                      const uint8_t *truncated, const uint8_t *was_reset, int32_t restart, const MgxEpisodeStats *stats,
+                      const MgxEpisodeTrace *trace, void *stream);
+int mgx_episode_restart(const MgxSpec *spec, int64_t batch, const uint8_t *select, const MgxEpisodeStats *stats, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,7 +28,8 @@ EXPORTS = ("mgx_abi_version", "mgx_error_string", "mgx_last_hip_error", "mgx_gen
            "mgx_step_ex", "mgx_step_tracked", "mgx_step_chains", "mgx_sub_shards",
            "mgx_pack_grid_env", "mgx_check_grid", "mgx_pack_grid8_env", "mgx_unpack_grid8", "mgx_shape_key", "mgx_shape_register", "mgx_stage_generate",
            "mgx_persistent_waves", "mgx_step_persistent", "mgx_persistent_post", "mgx_persistent_wait", "mgx_persistent_feed",
-           "mgx_rollout_info", "mgx_render_atlas", "mgx_render", "mgx_reset_select", "mgx_reset_generate_select")
+           "mgx_rollout_info", "mgx_render_atlas", "mgx_render", "mgx_reset_select", "mgx_reset_generate_select",
+           "mgx_episode_stats", "mgx_episode_restart")
 
 
 class MgxLaunchInfo(C.Structure):
@@ -84,6 +85,20 @@ class MgxPersistent(C.Structure):
 
 
 PERSIST_CTRL_WORDS = 8
+
+
+class MgxEpisodeStats(C.Structure):
+    """include/mgx.h: struct MgxEpisodeStats (the episode accounting's state)."""
+    _fields_ = [(n, C.c_void_p) for n in ("cur_return", "cur_length", "over", "last_return", "last_length", "sum_return",
+                                           "sum_length", "counts")]
+
+
+class MgxEpisodeTrace(C.Structure):
+    """include/mgx.h: struct MgxEpisodeTrace (the optional per-step outputs)."""
+    _fields_ = [(n, C.c_void_p) for n in ("closed", "episode_return", "episode_length")]
+
+
+RESTART_NONE, RESTART_BEFORE, RESTART_AFTER = 0, 1, 2
 
 GEN_KINDS = {"empty_fixed": 0, "empty_random": 1, "blockedunlockpickup": 2, "redbluedoors": 3, "lockedhallway": 4, "playground": 5}
 
@@ -180,6 +195,13 @@ def lib() -> C.CDLL:
     L.mgx_render_atlas.argtypes = [C.c_int32, vp, vp]
     L.mgx_render.restype = C.c_int
     L.mgx_render.argtypes = [C.POINTER(MgxSpecC), i64, vp, vp, vp, vp, C.c_int32, vp, vp]
+    # (an older build loaded through MGX_LIBMGX may lack the accounting: only an env that tracks episodes needs it)
+    if is_product_lib() or hasattr(L, "mgx_episode_stats"):
+        L.mgx_episode_stats.restype = C.c_int
+        L.mgx_episode_stats.argtypes = [C.POINTER(MgxSpecC), i64, C.c_int32, vp, vp, vp, vp, C.c_int32, C.POINTER(MgxEpisodeStats),
+                                        C.POINTER(MgxEpisodeTrace), vp]
+        L.mgx_episode_restart.restype = C.c_int
+        L.mgx_episode_restart.argtypes = [C.POINTER(MgxSpecC), i64, vp, C.POINTER(MgxEpisodeStats), vp]
     if L.mgx_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH}: ABI version {L.mgx_abi_version()} != {ABI_VERSION}; rebuild it")
     _lib = L

@@ -41,6 +41,61 @@ class StepGraph:
         self.graph.replay()
 
 
+class EpisodeStats:
+    """Returns, lengths and outcomes of the episodes of a BatchedMultiGridEnv, kept on the device by the env itself
+    (`BatchedMultiGridEnv.track_episodes()`; the rule: include/mgx.h "EPISODE ACCOUNTING").  The tensors, read-only by convention:
+
+        cur_return f64[B,A]  cur_length i32[B]   the running episode        over u8[B]  closed, and not restarted since
+        last_return f64[B,A] last_length i32[B]  the episode closed last
+        sum_return f64[B,A]  sum_length i64[B]   over all closed episodes   counts i32[B,4]  closed, terminated, rewarded, aborted
+
+    Everything is per env: a batch-level figure is a `sum()` at logging time (`summary()`)."""
+
+    TENSORS = (("cur_return", torch.float64, True), ("cur_length", torch.int32, False), ("over", torch.uint8, False),
+               ("last_return", torch.float64, True), ("last_length", torch.int32, False), ("sum_return", torch.float64, True),
+               ("sum_length", torch.int64, False), ("counts", torch.int32, 4))
+
+    def __init__(self, batch: int, num_agents: int, device, trace: bool = False, _tensors=None):
+        self.batch, self.num_agents, self.trace = int(batch), int(num_agents), bool(trace)
+        if _tensors is None:
+            _tensors = {}
+            for name, dt, per in self.TENSORS:
+                shape = (self.batch, num_agents) if per is True else ((self.batch, per) if per else (self.batch,))
+                _tensors[name] = torch.zeros(shape, dtype=dt, device=device)
+        self.tensors = _tensors          # name -> tensor, in the order of struct MgxEpisodeStats
+        for name, t in _tensors.items():
+            setattr(self, name, t)
+
+    def _slice(self, lo: int, hi: int) -> "EpisodeStats":
+        """The envs [lo, hi) as views (a sub-shard's share: BatchedMultiGridEnv.split)."""
+        return EpisodeStats(hi - lo, self.num_agents, None, self.trace, {n: t[lo:hi] for n, t in self.tensors.items()})
+
+    def summary(self) -> dict:
+        """The closed episodes of the whole batch as Python numbers, after ONE device-to-host copy: episodes, mean_return (per
+        agent), mean_length, the shares terminated / rewarded of the closed episodes, and the number aborted."""
+        A = self.num_agents
+        v = torch.cat((self.counts.sum(dim=0).to(torch.float64), self.sum_length.sum().to(torch.float64).reshape(1),
+                       self.sum_return.sum(dim=0))).cpu().tolist()
+        n = int(v[0])
+        d = float(max(n, 1))
+        return {"episodes": n, "mean_return": [x / d for x in v[5:5 + A]], "mean_length": v[4] / d, "terminated": v[1] / d,
+                "rewarded": v[2] / d, "aborted": int(v[3])}
+
+    def reset_totals(self):
+        """Zero the totals and the counters (a new logging window); running episodes are left alone."""
+        self.sum_return.zero_(); self.sum_length.zero_(); self.counts.zero_()
+
+    def state_dict(self) -> dict:
+        return {n: t.cpu().clone() for n, t in self.tensors.items()}
+
+    def load_state_dict(self, sd: dict):
+        for n, t in self.tensors.items():
+            if tuple(sd[n].shape) != tuple(t.shape):
+                raise ValueError(f"episode stats: {n} has shape {tuple(sd[n].shape)}, expected {tuple(t.shape)}")
+        for n, t in self.tensors.items():
+            t.copy_(sd[n])
+
+
 class PersistentSession:
     """Closed-loop stepping without a kernel boundary per step (include/mgx.h: mgx_step_persistent): ONE launch of the step kernel
     stays resident on a stream of its own, keeps the env state in LDS, takes each step's actions as tagged granules and publishes
@@ -235,6 +290,7 @@ class BatchedMultiGridEnv:
         self._chain_streams = []         # side streams of the eager sub-shard form (step(..., sub_shards=P))
         self._chains_pending, self._chains_P = False, 1
         self._session = None             # an open PersistentSession: the state lives in its launch
+        self._stats = None               # EpisodeStats while track_episodes() is on
         self.shape_kernel = None
         if specialise is None:
             specialise = os.environ.get("MGX_JIT", "0") not in ("", "0")
@@ -368,6 +424,8 @@ class BatchedMultiGridEnv:
         self._reset_err()
         self._state_written()
         self._loaded = True
+        if self._stats is not None:
+            self._rebase_episodes()
 
     def _refuse_carried_contents(self, agent_rows):
         """Compact cells (EnvSpec.cell_bytes = 1) have no room for what a box holds (include/mgx.h: MgxCell8): a filled box on the
@@ -501,6 +559,9 @@ class BatchedMultiGridEnv:
         if sub_shards != 1:
             P = self.sub_shards_hint(auto_reset or generate, one_hot, form="eager") if sub_shards == "auto" else int(sub_shards)
             P = max(1, min(P, self.batch // self.SUB_SHARD_ALIGN))
+        if P > 1 and self._stats is not None:
+            raise RuntimeError("episode accounting (track_episodes) does not follow an eager step(sub_shards=P > 1): its chains run "
+                               "on side streams; capture_steps(sub_shards=P) is the supported form")
         if self._chains_pending and P != self._chains_P:       # (another cut of the batch over other streams: join the old chains)
             self.join()
         key = (bool(auto_reset), bool(one_hot), generate, P)
@@ -546,8 +607,11 @@ class BatchedMultiGridEnv:
         self.backend.step(self.batch, self._cells, self.agents, self.rng, self.step_count, actions,
                           self.aux if sp.env_kind != "empty" else None, self.err,
                           obs, self.dir, self.reward, self.terminated, self.truncated, **kw)
+        if self._stats is not None:
+            self.backend.episode_stats(self.batch, 1, self.reward, self.terminated, self.truncated, self.was_reset if ar else None,
+                                       _lib.RESTART_BEFORE if ar else _lib.RESTART_NONE, self._stats.tensors)
         if generate:
-            self.reset_done()
+            self.reset_done()        # (with the accounting's restart clause behind it: together RESTART_AFTER)
         return obs, self.dir, self.reward, self.terminated, self.truncated
 
     def join(self):
@@ -604,14 +668,31 @@ class BatchedMultiGridEnv:
                  auto_reset=ar, one_hot=one_hot,
                  **({"generate": (self._gen, self.episode, self.was_reset)} if generate else {}),
                  **({"marker": self._marker} if track else {}))
+        if self._stats is not None and parts == 1:
+            f = self._with_accounting(f, ar is not None, generate)
         self._bound[key] = f
         return f
+
+    def _with_accounting(self, step, pool_restart: bool, generate: bool):
+        """The step launcher and the accounting launch directly behind it on the same stream as ONE launcher: what a tracking env
+        binds in place of the step's own, so that step()'s hot path stays one lookup and one call -- and an env that does not
+        track pays nothing."""
+        restart = _lib.RESTART_BEFORE if pool_restart else (_lib.RESTART_AFTER if generate else _lib.RESTART_NONE)
+        account = self.backend.bind_episode_stats(self.batch, self.reward, self.terminated, self.truncated,
+                                                  self.was_reset if restart != _lib.RESTART_NONE else None, restart, self._stats.tensors)
+
+        def tracked_step(actions, hook_order=None):
+            step(actions, hook_order)
+            account()
+        tracked_step._keep = (step, account)
+        tracked_step.tracked = getattr(step, "tracked", False)
+        return tracked_step
 
     def _check_fresh(self):
         """A sub-shard (or a captured graph) holds pointers into its parent's layout pool / generator tensors."""
         if self._parent is not None and self._parent._layout_version != self._made_version:
             raise RuntimeError("this sub-shard was split off before its parent's set_layout_pool() / set_layout_generator() "
-                               "replaced the layout tensors: split() / capture_steps() again")
+                               "replaced the layout tensors (or track_episodes() the accounting's): split() / capture_steps() again")
 
     # ------------------------------------------------------------------------------------------ sub-shards
     SUB_SHARD_ALIGN = 64         # envs: keeps every sub-shard's tensors 16-byte aligned and its wavefronts' tiles as in the whole
@@ -640,6 +721,7 @@ class BatchedMultiGridEnv:
             c._parent, c._made_version, c._layout_version = self, self._layout_version, 0
             c._chain_streams, c._chains_pending, c._chains_P, c._session = [], False, 1, None
             c._seeded = self._seeded
+            c._stats = self._stats._slice(lo, hi) if self._stats is not None else None
             c._one_hot = self._one_hot[lo:hi] if getattr(self, "_one_hot", None) is not None else None
             c._pool = getattr(self, "_pool", None)
             c._gen = None
@@ -751,13 +833,70 @@ class BatchedMultiGridEnv:
                                  self.aux if sp.env_kind != "empty" else None, self.err, out["obs"], out["dir"],
                                  out["reward"], out["terminated"], out["truncated"],
                                  generate=(self._gen, self.episode, out["was_reset"]), **({"one_hot": True} if one_hot else {}))
+            self._account_rollout(out, T, _lib.RESTART_AFTER)
             return out
         ar = self._auto_reset_args(auto_reset, out.get("was_reset"))
         self.backend.rollout(B, T, self._cells, self.agents, self.rng, self.step_count, actions,
                              self.aux if sp.env_kind != "empty" else None, self.err, out["obs"], out["dir"],
                              out["reward"], out["terminated"], out["truncated"],
                              **({"auto_reset": ar} if ar is not None else {}), **({"one_hot": True} if one_hot else {}))
+        self._account_rollout(out, T, _lib.RESTART_BEFORE if ar is not None else _lib.RESTART_NONE)
         return out
+
+    def _account_rollout(self, out: dict, T: int, restart: int):
+        """The accounting of a rollout: ONE launch over its [T,...] outputs; with track_episodes(trace=True) the result also gains
+        'episode_closed' u8[T,B], 'episode_return' f64[T,B,A] and 'episode_length' i32[T,B] (the closed episode's values at a closing
+        step, zeros elsewhere)."""
+        st = self._stats
+        if st is None:
+            return
+        trace = None
+        if st.trace:
+            B, A, dev = self.batch, self.spec.num_agents, self.device
+            for name, dt, shape in (("episode_closed", torch.uint8, (T, B)), ("episode_return", torch.float64, (T, B, A)),
+                                    ("episode_length", torch.int32, (T, B))):
+                if name not in out:
+                    out[name] = torch.empty(shape, dtype=dt, device=dev)
+            trace = {"closed": out["episode_closed"], "episode_return": out["episode_return"], "episode_length": out["episode_length"]}
+        self.backend.episode_stats(self.batch, T, out["reward"], out["terminated"], out["truncated"],
+                                   out["was_reset"] if restart != _lib.RESTART_NONE else None, restart, st.tensors, trace)
+
+    # ------------------------------------------------------------------------------------------ episode accounting
+    def track_episodes(self, trace: bool | None = False):
+        """Keep the return, the length and the outcome of every episode on the device (include/mgx.h "EPISODE ACCOUNTING"): what
+        gymnasium's RecordEpisodeStatistics, EnvPool's info["episode"] and gymnax' LogWrapper give their callers.  Returns the
+        `EpisodeStats` (also `.episode_stats`); `track_episodes(None)` stops.
+
+        From then on every stepping and restart form of this env issues the accounting launch itself, on the same stream, directly
+        behind the launch it accounts for: `step()` (one extra launch per step; captured with it by `capture_steps()`, sub-shards
+        included), `rollout()` (one launch over the T steps' outputs; trace=True: the result also holds 'episode_closed',
+        'episode_return', 'episode_length' per step), `reset_done()` / `reset(seed, mask)` (a restarted env's running episode is
+        counted as aborted), `load_state()` (every env restarts).  An episode ends where the step's OUTPUTS say so -- truncated,
+        or every agent terminated.  An env whose episode is already over when tracking starts is skipped until it restarts.
+        Sub-shards and graphs made before the call refuse to run.  Not available: `persistent()` (the state lives in the resident
+        launch) and the eager `step(sub_shards=P > 1)` -- both raise while tracking is on."""
+        self._no_session("track_episodes")
+        self.join()
+        self._bound.clear()              # (the launchers bound so far step without / with the accounting)
+        self._layout_version += 1        # (sub-shards and captured graphs made before hold the other form)
+        if trace is None:
+            self._stats = None
+            return None
+        self._stats = EpisodeStats(self.batch, self.spec.num_agents, self.device, trace=bool(trace))
+        if self._loaded:
+            self._stats.over.copy_(self.is_done())
+        return self._stats
+
+    @property
+    def episode_stats(self):
+        """The `EpisodeStats` of `track_episodes()`, or None."""
+        return self._stats
+
+    def _rebase_episodes(self):
+        """The whole state was replaced (load_state, the first reset): every env restarts, and one that is already over stays
+        out of the books until it is restarted."""
+        self.backend.episode_restart(self.batch, None, self._stats.tensors)
+        self._stats.over.copy_(self.is_done())
 
     # ------------------------------------------------------------------------------------------ either side of the path
     def one_hot_obs(self) -> torch.Tensor:
@@ -998,12 +1137,16 @@ class BatchedMultiGridEnv:
         if getattr(self, "_gen", None) is not None:
             self.backend.reset_generate(self.batch, self._gen, self._cells, self.agents, self.rng, self.step_count,
                                         self.aux if self.spec.env_kind != "empty" else None, self.episode, self.was_reset)
+            if self._stats is not None:
+                self.backend.episode_restart(self.batch, self.was_reset, self._stats.tensors)
             return self.was_reset
         if getattr(self, "_pool", None) is None:
             raise RuntimeError("call set_layout_pool() or set_layout_generator() first")
         self.backend.reset_done(self.batch, self.first_env, self._pool, self._cells, self.agents, self.step_count,
                                 self.aux, self.episode, self.was_reset)
         self._restarted()
+        if self._stats is not None:
+            self.backend.episode_restart(self.batch, self.was_reset, self._stats.tensors)
         return self.was_reset
 
     def reset(self, seed: int | None = None, mask: torch.Tensor | None = None, one_hot: bool = False):
@@ -1055,7 +1198,12 @@ class BatchedMultiGridEnv:
             self._restarted()
         if seed is not None:
             self._seeded = True
-        self._loaded = True
+        first, self._loaded = not self._loaded, True
+        if self._stats is not None:
+            if first:
+                self._rebase_episodes()
+            else:
+                self.backend.episode_restart(self.batch, self.was_reset, self._stats.tensors)
         return self.gen_obs(one_hot)
 
     def outputs_to_host(self) -> dict:
@@ -1125,6 +1273,9 @@ class BatchedMultiGridEnv:
         """A `PersistentSession` over this env: closed-loop stepping with ONE resident launch instead of one launch per step
         (include/mgx.h: mgx_step_persistent).  Same results as `step()` bit for bit.  `max_steps` bounds the launch; every wait
         inside it gives up after `timeout_ms`."""
+        if self._stats is not None:
+            raise RuntimeError("episode accounting (track_episodes) does not follow persistent stepping: the env state lives in the "
+                               "resident launch; track_episodes(None) first")
         if not (self.spec.cell_bytes == 1 and self.spec.env_kind == "empty"):
             self._need_wide_cells("persistent stepping")                    # (compact cells: the hook-free persistent launch, round 6)
         return PersistentSession(self, max_steps, auto_reset, timeout_ms)

@@ -475,5 +475,55 @@ class HipBackend:
                 step_count.data_ptr(), _ptr(aux), episode.data_ptr(), _ptr(was_reset), _stream(grid.device))
         _lib.check(rc, "mgx_reset_generate_select")
 
+    # ------------------------------------------------------------------------------------------ episode accounting
+    @staticmethod
+    def _episode_structs(stats, trace=None):
+        """stats = {name: tensor} of include/mgx.h MgxEpisodeStats; trace = {closed, episode_return, episode_length} (each may be
+        missing / None) or None"""
+        st = _lib.MgxEpisodeStats(*[stats[n].data_ptr() for n, _ in _lib.MgxEpisodeStats._fields_])
+        tr = None
+        if trace is not None:
+            tr = _lib.MgxEpisodeTrace(*[_ptr(trace.get(n)) for n, _ in _lib.MgxEpisodeTrace._fields_])
+        return st, tr
+
+    def episode_stats(self, B, T, reward, terminated, truncated, was_reset, restart, stats, trace=None):
+        """mgx_episode_stats on torch's current stream: the outputs of T steps ([T,...] tensors, or one step's) applied to the
+        accounting's state; `restart` = _lib.RESTART_* says what `was_reset` (None with RESTART_NONE) means."""
+        st, tr = self._episode_structs(stats, trace)
+        with torch.cuda.device(reward.device):
+            rc = _lib.lib().mgx_episode_stats(C.byref(self.sc), B, T, reward.data_ptr(), terminated.data_ptr(), truncated.data_ptr(),
+                                              _ptr(was_reset), restart, C.byref(st), C.byref(tr) if tr is not None else None,
+                                              _stream(reward.device))
+        _lib.check(rc, "mgx_episode_stats")
+
+    def episode_restart(self, B, select, stats):
+        """mgx_episode_restart: the restart clause for the envs of `select` (u8[B]; None = every env)."""
+        st, _ = self._episode_structs(stats)
+        dev = stats["over"].device
+        with torch.cuda.device(dev):
+            rc = _lib.lib().mgx_episode_restart(C.byref(self.sc), B, _ptr(select), C.byref(st), _stream(dev))
+        _lib.check(rc, "mgx_episode_restart")
+
+    def bind_episode_stats(self, B, reward, terminated, truncated, was_reset, restart, stats):
+        """The accounting of ONE step with every pointer resolved once, as bind_step does for the step: returns f() enqueuing it
+        on torch's current stream -- a tracked step costs this one extra call.  The tensors must stay alive and in place."""
+        st, _ = self._episode_structs(stats)
+        fn = _lib.lib().mgx_episode_stats
+        spec_ref, st_ref = C.byref(self.sc), C.byref(st)
+        rp, tp, up, wp = reward.data_ptr(), terminated.data_ptr(), truncated.data_ptr(), _ptr(was_reset)
+        dev, index = reward.device, reward.device.index
+        device_ctx = torch.cuda.device
+
+        def account():
+            if _cur_device() == index:
+                rc = fn(spec_ref, B, 1, rp, tp, up, wp, restart, st_ref, None, _stream(dev))
+            else:
+                with device_ctx(dev):
+                    rc = fn(spec_ref, B, 1, rp, tp, up, wp, restart, st_ref, None, _stream(dev))
+            if rc:
+                _lib.check(rc, "mgx_episode_stats")
+        account._keep = (st, stats, reward, terminated, truncated, was_reset)
+        return account
+
     def launch_info(self, B) -> dict:
         return _lib.launch_info(self.spec, B)
