@@ -737,6 +737,62 @@ int mgx_episode_stats(const MgxSpec *spec, int64_t batch, int32_t steps, const d
                       const MgxEpisodeTrace *trace, void *stream);
 int mgx_episode_restart(const MgxSpec *spec, int64_t batch, const uint8_t *select, const MgxEpisodeStats *stats, void *stream);
 
+/* ENV COPY (additive to ABI 11): snapshot, restore and fork of chosen envs on the device -- what `copy.deepcopy(env)` gives a user
+ * of the reference, for the envs the caller names, in ONE launch.  Build-defined: the reference has no batching.
+ *
+ * A STATE SET (MgxEnvRows) names the per-env rows of one holder of env state -- a live batch of envs, or a snapshot -- by pointer.
+ * `rows` is the number of rows it holds; a nullable member is NULL when the set has no such row:
+ *   cells       H * W * cell_bytes bytes per row, in the spec's cell format (any of the three)        required
+ *   agents      u8[rows,A,8]                                                                           required
+ *   rng         u64[rows,4]   env.np_random's PCG64 words                                              required
+ *   step_count  i32[rows]                                                                              required
+ *   aux         u8[rows,16]   the env subclass' hook state                                             nullable
+ *   marker      i32[rows]     the layout marker of mgx_step_tracked                                    nullable
+ *   episode     i32[rows]     the restart counter of MgxAutoReset / the generator                      nullable
+ *   gen_state   u64[rows,6]   MgxLayoutGen.gen_state                                                   nullable
+ *   cur_return f64[rows,A], cur_length i32[rows], over u8[rows]   the RUNNING TRIO of MgxEpisodeStats: all three, or none
+ *
+ * mgx_env_copy: for every pair i < n, row src_idx[i] of `src` is copied to row dst_idx[i] of `dst` (a NULL index array is the
+ * identity i):
+ *   MEMBERS      a member is copied when BOTH sets carry it; a member only one of them carries is left alone, except:
+ *   marker       dst->marker[d] = -1 when `src` has no marker, or when marker_fill != 0 (the caller knows that the layout indices of
+ *                the source no longer mean anything: another pool, another env);
+ *   running trio when `dst` has it and `src` has not: cur_return = 0, cur_length = 0, over = 0 -- a fresh episode, and nothing is
+ *                counted (no totals, no counters are part of a state set);
+ *   stage_tag    the DESTINATION's MgxGenStage.tag (i32[rows,4]; NULL: none).  For every destination row written the slots are
+ *                dropped (they are a cache: always valid): stage_mode 1 (candidates): all four words = -1; stage_mode 2 (snapshot
+ *                forms): [0] = -1, [3] = 0; stage_mode 0: the tags are left alone;
+ *   bad indices  a pair whose source or destination index is outside [0, rows) of its set is skipped WHOLE -- no byte of it is
+ *                written -- and counted: bad[0] += 1, bad[1] = min(bad[1], i) (the convention of the step's `err` words: start them
+ *                at {0, INT32_MAX}; i beyond INT32_MAX counts as INT32_MAX).  `bad` may be NULL: the pairs are skipped silently;
+ *   duplicates   destination indices must be distinct: what a row named twice ends up with is unspecified (some mix of its sources'
+ *                members), but never out of bounds.  Source indices may repeat: that is the fork;
+ *   aliasing     no row of `src` may overlap a row of `dst`.
+ * Everything else a step hands back (obs, reward, ...) is no part of a state set: mgx_gen_obs after a restore.
+ *
+ * Return codes: a bad spec (NULL, num_agents outside 1..MGX_MAX_AGENTS, an unknown cell_bytes), n < 0, NULL `src` / `dst`,
+ * rows < 0, stage_mode outside 0..2: MGX_ERR_INVALID_ARGUMENT; then n == 0: MGX_OK, nothing is launched; then a NULL required member,
+ * a running trio with only some of its three pointers, or a misaligned member -- 16 bytes for rng, aux, gen_state and stage_tag
+ * (they move as 16-byte vectors), 8 for agents, cur_return and the index arrays, 4 for the i32 members and `bad`, 2 for 16-bit cells --
+ * MGX_ERR_INVALID_ARGUMENT; more than INT_MAX workgroups: MGX_ERR_UNSUPPORTED. */
+typedef struct MgxEnvRows {
+    void *cells;
+    uint8_t *agents;
+    uint64_t *rng;
+    int32_t *step_count;
+    uint8_t *aux;
+    int32_t *marker;
+    int32_t *episode;
+    uint64_t *gen_state;
+    double *cur_return;
+    int32_t *cur_length;
+    uint8_t *over;
+    int64_t rows;
+} MgxEnvRows;
+
+int mgx_env_copy(const MgxSpec *spec, int64_t n, const MgxEnvRows *src, const int64_t *src_idx, const MgxEnvRows *dst,
+                 const int64_t *dst_idx, int32_t *stage_tag, int32_t stage_mode, int32_t marker_fill, int32_t *bad, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

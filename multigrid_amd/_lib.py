@@ -29,7 +29,7 @@ EXPORTS = ("mgx_abi_version", "mgx_error_string", "mgx_last_hip_error", "mgx_gen
            "mgx_pack_grid_env", "mgx_check_grid", "mgx_pack_grid8_env", "mgx_unpack_grid8", "mgx_shape_key", "mgx_shape_register", "mgx_stage_generate",
            "mgx_persistent_waves", "mgx_step_persistent", "mgx_persistent_post", "mgx_persistent_wait", "mgx_persistent_feed",
            "mgx_rollout_info", "mgx_render_atlas", "mgx_render", "mgx_reset_select", "mgx_reset_generate_select",
-           "mgx_episode_stats", "mgx_episode_restart")
+           "mgx_episode_stats", "mgx_episode_restart", "mgx_env_copy")
 
 
 class MgxLaunchInfo(C.Structure):
@@ -99,6 +99,15 @@ class MgxEpisodeTrace(C.Structure):
 
 
 RESTART_NONE, RESTART_BEFORE, RESTART_AFTER = 0, 1, 2
+
+
+class MgxEnvRows(C.Structure):
+    """include/mgx.h: struct MgxEnvRows (the per-env rows of one state set: a batch of envs, or a snapshot)."""
+    _fields_ = [(n, C.c_void_p) for n in ("cells", "agents", "rng", "step_count", "aux", "marker", "episode", "gen_state",
+                                           "cur_return", "cur_length", "over")] + [("rows", C.c_int64)]
+
+
+STAGE_NONE, STAGE_CANDIDATES, STAGE_SNAPSHOTS = 0, 1, 2      # mgx_env_copy's stage_mode
 
 GEN_KINDS = {"empty_fixed": 0, "empty_random": 1, "blockedunlockpickup": 2, "redbluedoors": 3, "lockedhallway": 4, "playground": 5}
 
@@ -202,6 +211,11 @@ def lib() -> C.CDLL:
                                         C.POINTER(MgxEpisodeTrace), vp]
         L.mgx_episode_restart.restype = C.c_int
         L.mgx_episode_restart.argtypes = [C.POINTER(MgxSpecC), i64, vp, C.POINTER(MgxEpisodeStats), vp]
+    # (... or the env copy: only snapshot() / restore() / fork() need it)
+    if is_product_lib() or hasattr(L, "mgx_env_copy"):
+        L.mgx_env_copy.restype = C.c_int
+        L.mgx_env_copy.argtypes = [C.POINTER(MgxSpecC), i64, C.POINTER(MgxEnvRows), vp, C.POINTER(MgxEnvRows), vp, vp, C.c_int32,
+                                   C.c_int32, vp, vp]
     if L.mgx_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH}: ABI version {L.mgx_abi_version()} != {ABI_VERSION}; rebuild it")
     _lib = L

@@ -13,6 +13,7 @@ Outputs of `step` (pre-allocated, overwritten by every call -- clone what you ke
 from __future__ import annotations
 
 import os
+import weakref
 
 import numpy as np
 import torch
@@ -94,6 +95,41 @@ class EpisodeStats:
                 raise ValueError(f"episode stats: {n} has shape {tuple(sd[n].shape)}, expected {tuple(t.shape)}")
         for n, t in self.tensors.items():
             t.copy_(sd[n])
+
+
+class EnvSnapshot:
+    """The state of `rows` envs of a BatchedMultiGridEnv as a value (`BatchedMultiGridEnv.snapshot()`), in device tensors of its own
+    (`.tensors`: member -> tensor with `rows` leading rows, the members of include/mgx.h MgxEnvRows the env carried):
+
+        cells (the env's own format)  agents  rng  step_count  aux  marker
+        episode     with a layout pool or a generator        gen_state   with a generator
+        cur_return, cur_length, over   the running episode, while track_episodes() was on
+
+    What a step hands back (obs, reward, ...) is no part of it: `gen_obs()` after a restore.  It remembers the spec, the kind of
+    restart source, and which env it came from at which `_layout_version` (only there do its layout markers mean anything)."""
+
+    MEMBERS = tuple(n for n, _ in _lib.MgxEnvRows._fields_[:-1])
+
+    def __init__(self, spec, rows: int, tensors: dict, source: tuple):
+        self.spec, self.rows, self.tensors, self.source = spec, int(rows), tensors, source
+        self.layout_version, self._layout_epoch, self._env, self._armed, self._seeded = 0, 0, None, False, False
+
+    def _taken_from(self, env):
+        self.layout_version, self._layout_epoch, self._env = env._layout_version, env._layout_epoch, weakref.ref(env)
+        self._armed, self._seeded = bool(env._mark["armed"]), env._seeded
+
+    def _is_of(self, env) -> bool:
+        """Taken from this very env, and its layout pool has not been replaced or refilled since."""
+        return (self._env is not None and self._env() is env and self.layout_version == env._layout_version
+                and self._layout_epoch == env._layout_epoch)
+
+    @property
+    def device(self):
+        return self.tensors["cells"].device
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in self.tensors.values())
 
 
 class PersistentSession:
@@ -291,6 +327,8 @@ class BatchedMultiGridEnv:
         self._chains_pending, self._chains_P = False, 1
         self._session = None             # an open PersistentSession: the state lives in its launch
         self._stats = None               # EpisodeStats while track_episodes() is on
+        self._layout_epoch = 0           # bumped whenever the layouts the marker's indices name change (an in-place refill included)
+        self._copy_bad = None            # i32[2]: the pairs snapshot() / restore() skipped (out of range), the first of them
         self.shape_kernel = None
         if specialise is None:
             specialise = os.environ.get("MGX_JIT", "0") not in ("", "0")
@@ -998,6 +1036,7 @@ class BatchedMultiGridEnv:
         self.join()
         cells = torch.from_numpy(layouts.pack_cells_for(sp, g.numpy()))
         old = getattr(self, "_pool", None)
+        self._layout_epoch += 1          # (a snapshot's layout markers spoke of the old layouts)
         if (getattr(self, "_gen", None) is None and old is not None and old[0].shape == cells.shape and old[1].shape == a.shape
                 and (old[2] is None) == (t is None)):
             # same shapes: refill the tensors in place -- sub-shards, pre-bound launchers and captured graphs stay valid
@@ -1121,6 +1160,7 @@ class BatchedMultiGridEnv:
                                   "aux": torch.zeros((B, 16), dtype=torch.uint8, device=dev) if sp.env_kind != "empty" else None,
                                   "words": torch.zeros((B, 12), dtype=torch.int64, device=dev), "tag": tag, "phase": [0]}
         self._disarm()                   # (no pool: nothing keeps the layout marker any more)
+        self._layout_epoch += 1
         self._pool = None
         self.episode = torch.zeros((self.batch,), dtype=torch.int32, device=self.device)
         self.was_reset = torch.zeros((self.batch,), dtype=torch.uint8, device=self.device)
@@ -1206,6 +1246,142 @@ class BatchedMultiGridEnv:
                 self.backend.episode_restart(self.batch, self.was_reset, self._stats.tensors)
         return self.gen_obs(one_hot)
 
+    # ------------------------------------------------------------------------------------------ snapshot / restore / fork
+    def _restart_source(self) -> tuple:
+        """The kind of this env's restart source: ("none",), ("pool",) or ("gen", generator kind)."""
+        if getattr(self, "_gen", None) is not None:
+            return ("gen", self._gen["kind"])
+        return ("pool",) if getattr(self, "_pool", None) is not None else ("none",)
+
+    def _state_rows(self) -> dict:
+        """This env as a state set (include/mgx.h: MgxEnvRows): every tensor that makes an env continue as it does -- the public
+        state, and the three pieces of engine state beside it (the layout marker, the generator's words, the running episode)."""
+        rows = {"cells": self._cells, "agents": self.agents, "rng": self.rng, "step_count": self.step_count, "aux": self.aux,
+                "marker": self._marker}
+        if self._restart_source() != ("none",):
+            rows["episode"] = self.episode
+        if getattr(self, "_gen", None) is not None:
+            rows["gen_state"] = self._gen["gen_state"]
+        if self._stats is not None:
+            rows.update(cur_return=self._stats.cur_return, cur_length=self._stats.cur_length, over=self._stats.over)
+        return rows
+
+    def _copy_entry(self, what: str):
+        self._no_session(what)
+        self._need_state()
+        if self._parent is not None:
+            raise RuntimeError(f"{what}: this env is a sub-shard of split() -- a view of its parent's tensors; {what} on the parent")
+        if self._copy_bad is None:
+            self._copy_bad = torch.tensor([0, INT32_MAX], dtype=torch.int32).to(self.device)
+        self.join()
+
+    def _index_arg(self, what: str, name: str, t, check_below=None, distinct: bool = False):
+        if not torch.is_tensor(t) or t.dtype is not torch.int64 or t.dim() != 1 or t.device != self._cells.device \
+                or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be a contiguous int64 tensor of shape (n,) on {self._cells.device}")
+        if check_below is not None and t.numel():
+            lo, hi = (int(v) for v in torch.stack((t.min(), t.max())).tolist())
+            if lo < 0 or hi >= check_below:
+                raise ValueError(f"{what}: {name} must lie in [0, {check_below}), got {lo}..{hi}")
+            if distinct and int(torch.unique(t).numel()) != t.numel():
+                raise ValueError(f"{what}: {name} names an env more than once")
+        return t
+
+    def snapshot(self, env_ids: torch.Tensor | None = None, out: EnvSnapshot | None = None) -> EnvSnapshot:
+        """The state of the envs `env_ids` as an `EnvSnapshot`, taken on the device by ONE launch (mgx_env_copy) on the current
+        stream: no host round trip, no synchronisation.  Row i of the snapshot is env env_ids[i].
+
+        env_ids  a contiguous int64 [n] tensor on the env's device (None = every env, in order), read by the kernel as it is.  An
+                 id outside [0, batch) is skipped, leaves its row as it was, and is reported by `check_errors()`.
+        out      a snapshot of the same row count and members (one this env made before) to overwrite: a planner that snapshots
+                 every step allocates nothing.
+        See `restore()` for what a restored env is."""
+        self._copy_entry("snapshot")
+        src = self._state_rows()
+        n = self.batch if env_ids is None else int(self._index_arg("snapshot", "env_ids", env_ids).shape[0])
+        if out is not None:
+            if not isinstance(out, EnvSnapshot) or out.spec != self.spec or out.rows != n or set(out.tensors) != set(src) \
+                    or out.device != self._cells.device or out.source != self._restart_source():
+                raise ValueError(f"snapshot: out= has another shape: it must be a snapshot of {n} row(s) of this env, with the members "
+                                 f"{sorted(src)}")
+            snap = out
+        else:
+            tensors = {m: torch.zeros((n,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device) for m, t in src.items()}
+            snap = EnvSnapshot(self.spec, n, tensors, self._restart_source())
+        snap._taken_from(self)
+        self.backend.env_copy(n, src, self.batch, env_ids, snap.tensors, n, None, None, _lib.STAGE_NONE, False, self._copy_bad)
+        return snap
+
+    def restore(self, snap: EnvSnapshot, env_ids: torch.Tensor | None = None, rows: torch.Tensor | None = None,
+                check: bool = False) -> None:
+        """Put the envs `env_ids` back to rows of a snapshot, on the device, by ONE launch (mgx_env_copy) on the current stream:
+        env env_ids[i] takes snapshot row rows[i].  The state tensors are written in place: pre-bound launchers and graphs from
+        `capture_steps` stay valid (and a `torch.cuda.graph` may capture the call).  Outputs are not restored: `gen_obs()`.
+
+        A restored env continues bit for bit as the env the row was taken from continued from the moment of the snapshot -- the
+        grid, the agents, np_random, the step count, the hook state, and the engine state beside them (the layout marker, the
+        running episode of `track_episodes()`):
+          * with a layout generator this holds across episode ends too: the placement generator's words, np_random and the
+            episode counter travel with the row (the staged generator's slots of the restored envs are dropped: a cache);
+          * with a layout pool it holds up to the env's next restart.  From there the SLOT's own rule applies -- layout =
+            (first_env + b + episode * 7919) mod K is a function of the slot b -- so forks of one source part at their first restart.
+
+        env_ids  contiguous int64 [n] on the env's device (None = every env, in order); they must be distinct
+        rows     contiguous int64 [n] (None = 0..n-1); rows may repeat: that is the fork
+        check    True: the range of both and the distinctness of env_ids are verified with torch ops -- a synchronisation -- and
+                 a ValueError names the fault.  False (default) trusts the caller: a pair out of range is skipped whole and
+                 reported by `check_errors()`; the result of a duplicate env id is unspecified.
+        The snapshot may come from another env object of equal spec and equal restart source (its layout markers then come out
+        unknown).  A snapshot without the running episode restored into a tracking env starts a fresh episode there; nothing is
+        counted as aborted."""
+        self._copy_entry("restore")
+        if not isinstance(snap, EnvSnapshot):
+            raise TypeError("restore: not an EnvSnapshot")
+        if snap.spec != self.spec:
+            raise ValueError("restore: the snapshot was taken from an env of a different EnvSpec")
+        if snap.source != self._restart_source():
+            raise ValueError(f"restore: the snapshot's restart source {snap.source} differs in kind from this env's "
+                             f"{self._restart_source()} (layout generator kind / layout pool / none)")
+        if snap.device != self._cells.device:
+            raise ValueError(f"restore: the snapshot lives on {snap.device}, this env on {self._cells.device}")
+        if env_ids is not None:
+            self._index_arg("restore", "env_ids", env_ids, self.batch if check else None, distinct=True)
+        if rows is not None:
+            self._index_arg("restore", "rows", rows, snap.rows if check else None)
+        n = self.batch if env_ids is None else int(env_ids.shape[0])
+        if rows is not None and int(rows.shape[0]) != n:
+            raise ValueError(f"restore: rows has {int(rows.shape[0])} entries for {n} env(s): env_ids[i] takes snapshot row rows[i]")
+        if rows is None and n > snap.rows:
+            raise ValueError(f"restore: {n} env(s) to restore, the snapshot holds {snap.rows} row(s): pass rows=")
+        gen = getattr(self, "_gen", None)
+        st = (gen or {}).get("stage")
+        if st is not None and st.get("stream") is not None:      # (generator launches beside the steps read gen_state / rng: behind them)
+            torch.cuda.current_stream(self.device).wait_stream(st["stream"])
+        tag, mode = None, _lib.STAGE_NONE
+        if st is not None:
+            tag, mode = st["tag"], (_lib.STAGE_CANDIDATES if st.get("candidates") else _lib.STAGE_SNAPSHOTS)
+        keep = snap._is_of(self)             # (only there do the snapshot's layout indices name this env's layouts)
+        if keep and snap._armed:             # markers >= 0 may be written -- by every replay, when a graph captures the call
+            m = self._mark
+            if not m["graphs"]:
+                m["armed"] = True
+                if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                    m["graphs"] = True
+        self.backend.env_copy(n, snap.tensors, snap.rows, rows, self._state_rows(), self.batch, env_ids, tag, mode, not keep,
+                              self._copy_bad)
+        self._seeded = self._seeded or snap._seeded
+
+    def fork(self, src_ids: torch.Tensor, dst_ids: torch.Tensor, check: bool = False) -> None:
+        """Copy the state of env src_ids[i] into env dst_ids[i] (contiguous int64 [n] tensors on the env's device; sources may
+        repeat, destinations must be distinct): `restore(snapshot(src_ids), dst_ids)`, two launches through a snapshot of n rows --
+        so a destination may also be somebody's source.  `check` as in `restore()`."""
+        self._copy_entry("fork")
+        self._index_arg("fork", "src_ids", src_ids, self.batch if check else None)
+        self._index_arg("fork", "dst_ids", dst_ids)
+        if src_ids.shape[0] != dst_ids.shape[0]:
+            raise ValueError(f"fork: {int(src_ids.shape[0])} source(s) for {int(dst_ids.shape[0])} destination(s)")
+        self.restore(self.snapshot(src_ids), dst_ids, check=check)
+
     def outputs_to_host(self) -> dict:
         """Everything the last step / gen_obs handed back, on the host after ONE device-to-host copy (into a pinned buffer) and one
         stream synchronisation: {'reward' f64[B,A], 'obs' u8[B,A,v,v,3], 'dir', 'terminated' u8[B,A], 'truncated' u8[B], 'err'
@@ -1229,7 +1405,8 @@ class BatchedMultiGridEnv:
         return out
 
     def check_errors(self):
-        """Synchronises and raises ValueError if any env met an unknown action since the last check."""
+        """Synchronises and raises ValueError if any env met an unknown action since the last check -- or, after that, if
+        snapshot() / restore() / fork() skipped a pair whose env id or snapshot row was out of range."""
         self.join()
         gb = getattr(self.backend, "_grid_bad", None)
         if gb is not None:                       # byte grids: what the step kernels counted while packing them
@@ -1243,6 +1420,13 @@ class BatchedMultiGridEnv:
             self._reset_err()
             raise ValueError(f"Unknown action in {count} env(s); first at local env {first} "
                              f"(valid: {int(Action.left)}..{int(Action.done)}, or {NO_ACTION} for no action)")
+        cb = getattr(self, "_copy_bad", None)
+        if cb is not None:                       # snapshot() / restore() / fork(): the pairs the kernel skipped
+            count, first = (int(v) for v in cb.cpu())
+            if count:
+                cb.copy_(torch.tensor([0, INT32_MAX], dtype=torch.int32))
+                raise ValueError(f"snapshot / restore / fork: {count} pair(s) named an env id or a snapshot row out of range and "
+                                 f"were skipped; first at pair {first}")
 
     def is_done(self) -> torch.Tensor:
         """multigrid/base.py:534-539 per env: bool[B]."""

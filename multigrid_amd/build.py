@@ -28,7 +28,7 @@ VIEWS = (3, 5, 7, 9, 11, 13, 15)
 #: that the units compile in parallel (a single unit took a minute).
 UNITS = ([("mgx_kernels", os.path.join(CSRC, "mgx_kernels.hip"), ()), ("mgx_aux", os.path.join(CSRC, "mgx_aux.hip"), ()),
           ("mgx_layout_gen", os.path.join(CSRC, "mgx_layout_gen.hip"), ()), ("mgx_render", os.path.join(CSRC, "mgx_render.hip"), ()),
-          ("mgx_stats", os.path.join(CSRC, "mgx_stats.hip"), ())]
+          ("mgx_stats", os.path.join(CSRC, "mgx_stats.hip"), ()), ("mgx_env_copy", os.path.join(CSRC, "mgx_env_copy.hip"), ())]
          + [(f"mgx_fused_v{v}", os.path.join(CSRC, "mgx_fused_inst.hip"), (f"MGX_INST_V={v}",)) for v in VIEWS])
 SRCS = sorted({u[1] for u in UNITS})
 DEPS = SRCS + [os.path.join(CSRC, "mgx_aux_geom.h"), os.path.join(CSRC, "mgx_fused.h"), os.path.join(CSRC, "mgx_fused_body.inc"), os.path.join(CSRC, "mgx_host.h"), os.path.join(CSRC, "mgx_layout_gen.h"), os.path.join(CSRC, "mgx_rules.h"),

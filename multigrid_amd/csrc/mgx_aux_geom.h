@@ -74,6 +74,35 @@ inline ResetUnit reset_copy_unit(int env_bytes, uintptr_t grid, uintptr_t pool_g
     return r;
 }
 
+// env_copy (mgx_env_copy.hip): the same choice for a copy between two state sets whose env rows the CALLER picks.  A row sits at an
+// arbitrary multiple of the tile size behind its base, so the unit has to divide the tile size and both bases -- and nothing else:
+// tile_bytes % unit == 0 and base % unit == 0 make every row's address a multiple of the unit.
+inline ResetUnit env_copy_unit(int tile_bytes, uintptr_t src, uintptr_t dst) { return reset_copy_unit(tile_bytes, src, dst); }
+
+// env_copy: a wavefront owns `run` consecutive (source, destination) pairs -- as many as make up about kEnvCopyWaveBytes of tile
+// bytes, at most one per lane, at least one (a tile beyond the bound is one pair per wavefront: run * tile_bytes <=
+// max(kEnvCopyWaveBytes, tile_bytes)).  A launch too small to give every SIMD of the chip a wavefront halves the run until it does or
+// the run is 1 (as full_obs_geom does).  Wavefront w takes the pairs [w * run, min((w + 1) * run, n)): none is left without a pair.
+constexpr int kEnvCopyWaveBytes = 4096;
+constexpr int kEnvCopyWpb = 4;                   // wavefronts per workgroup
+constexpr int64_t kEnvCopyFillWaves = 1024;      // 256 CUs x 4 SIMDs
+
+struct EnvCopyGeom {
+    int run;                // pairs per wavefront, 1..64
+    int64_t nwaves, blocks;
+};
+
+inline EnvCopyGeom env_copy_geom(int tile_bytes, int64_t n) {
+    EnvCopyGeom g;
+    g.run = kEnvCopyWaveBytes / (tile_bytes < 1 ? 1 : tile_bytes);
+    if (g.run > 64) g.run = 64;
+    if (g.run < 1) g.run = 1;
+    while (g.run > 1 && (n + g.run - 1) / g.run < kEnvCopyFillWaves) g.run = (g.run + 1) / 2;
+    g.nwaves = (n + g.run - 1) / g.run;
+    g.blocks = (g.nwaves + kEnvCopyWpb - 1) / kEnvCopyWpb;
+    return g;
+}
+
 // persistent stepping: granules (4 action bytes each) per env and in all, and the reciprocal the producer kernels find a granule's
 // env with -- g / gpe by recip32, so the batch ends where that stops being exact (recip32_exact_below: 2^30 granules at gpe = 5,
 // 1 431 655 766 at gpe = 7, beyond 2^31 at every other gpe <= 8) or at 2^31 granules, whichever comes first

@@ -525,5 +525,22 @@ class HipBackend:
         account._keep = (st, stats, reward, terminated, truncated, was_reset)
         return account
 
+    # ------------------------------------------------------------------------------------------ snapshot / restore / fork
+    @staticmethod
+    def _env_rows(rows: dict, n: int):
+        """rows = {member: tensor or None} of include/mgx.h MgxEnvRows (missing = None), `n` = the rows the set holds"""
+        return _lib.MgxEnvRows(*[_ptr(rows.get(m)) for m, _ in _lib.MgxEnvRows._fields_[:-1]], n)
+
+    def env_copy(self, n, src, src_rows, src_idx, dst, dst_rows, dst_idx, stage_tag, stage_mode, marker_fill, bad):
+        """mgx_env_copy on torch's current stream: for i < n, row src_idx[i] of the state set `src` (a dict of tensors, `src_rows`
+        rows) -> row dst_idx[i] of `dst`; the index tensors (i64[n] on the device, None = the identity) are read by the kernel as
+        they are.  `stage_tag` / `stage_mode`: the destination's staging tags (or None / _lib.STAGE_NONE); `bad` i32[2]."""
+        s, d = self._env_rows(src, src_rows), self._env_rows(dst, dst_rows)
+        dev = dst["cells"].device
+        with torch.cuda.device(dev):
+            rc = _lib.lib().mgx_env_copy(C.byref(self.sc), n, C.byref(s), _ptr(src_idx), C.byref(d), _ptr(dst_idx), _ptr(stage_tag),
+                                         stage_mode, int(bool(marker_fill)), _ptr(bad), _stream(dev))
+        _lib.check(rc, "mgx_env_copy")
+
     def launch_info(self, B) -> dict:
         return _lib.launch_info(self.spec, B)
