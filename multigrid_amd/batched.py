@@ -867,10 +867,24 @@ class BatchedMultiGridEnv:
             out["was_reset"] = torch.empty((T, B), dtype=torch.uint8, device=dev)
         generate = bool(auto_reset) and getattr(self, "_gen", None) is not None
         if generate:        # episode starts generated on the device: the envs whose episode ends with step t are regenerated
-            self.backend.rollout(B, T, self._cells, self.agents, self.rng, self.step_count, actions,          # right after it
-                                 self.aux if sp.env_kind != "empty" else None, self.err, out["obs"], out["dir"],
-                                 out["reward"], out["terminated"], out["truncated"],
-                                 generate=(self._gen, self.episode, out["was_reset"]), **({"one_hot": True} if one_hot else {}))
+            aux, oh = self.aux if sp.env_kind != "empty" else None, {"one_hot": True} if one_hot else {}          # right after it
+            if T > 1 and out["obs"][0].numel() % 16 and hasattr(self.backend, "stage_generate"):
+                # T launches of the one-step kernel, which writes its observations from a 16-byte aligned base: where a step's
+                # observations are no multiple of 16 bytes (130 envs x 2 agents x 27) the [t] slices of `obs` are not aligned, and
+                # the launcher refuses slice 1 with step 0 already taken.  Each step then writes an aligned buffer and is copied
+                # into place; the generator launches between the steps keep their cadence (ops.HipBackend.bind_step).
+                scratch, st = torch.empty_like(out["obs"][:1]), self._gen.get("stage")
+                for t in range(T):
+                    self.backend.rollout(B, 1, self._cells, self.agents, self.rng, self.step_count, actions[t:t + 1], aux, self.err,
+                                         scratch, out["dir"][t:t + 1], out["reward"][t:t + 1], out["terminated"][t:t + 1],
+                                         out["truncated"][t:t + 1], generate=(self._gen, self.episode, out["was_reset"][t:t + 1]), **oh)
+                    out["obs"][t:t + 1].copy_(scratch)
+                    if st is not None and st.get("external") == 2 and st["phase"][0] % max(1, int(st.get("lead", 2)) // 2) == 0:
+                        self.backend.stage_generate(B, self._gen, self.rng, self.episode)
+            else:
+                self.backend.rollout(B, T, self._cells, self.agents, self.rng, self.step_count, actions, aux, self.err, out["obs"],
+                                     out["dir"], out["reward"], out["terminated"], out["truncated"],
+                                     generate=(self._gen, self.episode, out["was_reset"]), **oh)
             self._account_rollout(out, T, _lib.RESTART_AFTER)
             return out
         ar = self._auto_reset_args(auto_reset, out.get("was_reset"))

@@ -1,0 +1,162 @@
+"""Random call sequences through BatchedMultiGridEnv on the HIP backend (the driver: tests/env_sequences.py; the same lists on two
+oracle-backed envs: tests/test_env_sequences.py).
+
+  * HIP against the oracle: one env on `HipBackend`, its twin on the CPU model of every launcher (`SeqOracle`); the lists of the CPU
+    file with the GPU-only kinds switched on -- a captured graph replayed twice, a graph kept and replayed again later, a persistent
+    session, step(sub_shards=2) + join(); every member compared byte for byte after every call, both marker rules on the HIP env;
+  * the time machine on the device, where it also covers the staged generator's slots;
+  * the size that READS the layout marker: 32 784 envs (more than 2048 wavefronts) on a one-layout pool, against a second HIP env whose
+    steps are bound untracked (`_tracks` replaced on the instance): every third call a step(auto_reset=True) that would trust a
+    stale marker, cell edits that land in marked envs and change what they observe;
+  * the pinned cases of the CPU file against the oracle."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from multigrid_amd import BatchedMultiGridEnv, layouts, rng as rnglib
+from tests import env_sequences as es
+from tests.test_env_sequences import time_machine
+from tests.test_grid_layout_marker import THROUGHPUT
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+SEQUENCES = [(130, 1), (130, 2), (7, 4)]
+N_OPS = 120
+
+
+def live_slots(env, op) -> int:
+    """how many of the envs this call writes hold a staging slot whose tag is live (not the empty value), read just before it"""
+    st = (getattr(env, "_gen", None) or {}).get("stage")
+    if st is None or op["kind"] not in ("restore", "reset", "seed"):
+        return 0
+    tag = st["tag"].cpu()
+    live = (tag != -1).any(dim=1) if st.get("candidates") else tag[:, 0] != -1
+    if op["kind"] == "restore" and op["env_ids"] is not None:
+        return int(live[torch.from_numpy(op["env_ids"])].sum())
+    if op["kind"] == "reset" and op["mask"] is not None:
+        return int(live[torch.from_numpy(op["mask"].astype(bool))].sum())
+    return int(live.sum())
+
+
+@functools.lru_cache(maxsize=None)
+def sequence(form, B, seed):
+    ops = es.make_ops(form, B, N_OPS, seed, gpu=True)
+    hip, twin = es.make_env(form, B, DEV), es.make_env(form, B)
+    ch, ct = es.new_ctx(), es.new_ctx()
+    seen = {"live_slots": 0, "tracked_entry": False}
+    for i, op in enumerate(ops):
+        where = es.where_text(form, B, seed, i, ops)
+        seen["live_slots"] += live_slots(hip, op)
+        oh, ot = es.apply(hip, op, ch), es.apply(twin, op, ct)
+        es.invariants(hip, where)
+        es.invariants(twin, where)
+        es.check_shadow(twin, where)
+        es.compare(hip, twin, ch, ct, where, oh, ot)
+        ent = hip._bound.get((True, False))
+        seen["tracked_entry"] = seen["tracked_entry"] or bool(ent and ent[2])
+    return ops, twin.backend, seen
+
+
+@pytest.mark.parametrize("B,seed", SEQUENCES)
+@pytest.mark.parametrize("form", es.FORMS)
+def test_hip_equals_the_oracle_after_every_call(form, B, seed):
+    ops, be, seen = sequence(form, B, seed)
+    assert len(ops) == N_OPS
+
+
+@pytest.mark.parametrize("form", es.FORMS)
+def test_census(form):
+    runs = [sequence(form, B, seed) for B, seed in SEQUENCES]
+    c = es.census_of([r[0] for r in runs], [r[1] for r in runs])
+    es.assert_census(c, form, 130, gpu=True)
+    if form in ("gen_candidates", "gen_between", "bup_candidates"):
+        assert sum(r[2]["live_slots"] for r in runs) > 0, "no restore / reset(mask) / seed met a live staging slot"
+    if form in ("pool1", "pool4_objects"):
+        assert any(r[2]["tracked_entry"] for r in runs), "step(auto_reset=True) never ran through the tracked hot-path entry"
+
+
+@pytest.mark.parametrize("form", es.FORMS)
+def test_time_machine(form):
+    kinds = {o["kind"] for o in time_machine(form, 130, 5, device=DEV, gpu=True)}
+    assert kinds <= set(es.PURE_KINDS) and "step" in kinds and "restore" in kinds
+
+
+@pytest.mark.parametrize("name", list(es.PINNED))
+def test_pinned(name):
+    case = es.PINNED[name]()
+    form, B, ops = case["form"], case["B"], case["ops"]
+    hip, twin = es.make_env(form, B, DEV), es.make_env(form, B)
+    ch, ct = es.new_ctx(), es.new_ctx()
+    for i, op in enumerate(ops):
+        where = f"pinned case {name}: call {i}: {es.describe(op)}"
+        oh, ot = es.apply(hip, op, ch), es.apply(twin, op, ct)
+        es.invariants(hip, where)
+        es.compare(hip, twin, ch, ct, where, oh, ot)
+        if i in case.get("checks", {}):
+            case["checks"][i](hip, where)
+
+
+# ---- the size that reads the marker -------------------------------------------------------------------------------------------------
+
+BIG_KINDS = ("step", "step_one_hot", "rollout", "reset_done", "reset", "snapshot", "snapshot_out", "restore", "fork", "edit",
+             "pool_refill", "track", "reset_totals", "seed", "gen_obs", "one_hot_obs", "split", "capture_replay", "graph_again",
+             "step_chains")
+BIG_WEIGHTS = {"edit": 6, "rollout": 4, "restore": 4, "snapshot": 3, "capture_replay": 3, "graph_again": 2, "track": 1, "step": 3}
+
+
+def big_env(form, tracked):
+    spec, B = es.SPECS[form], THROUGHPUT
+    if form == "big_empty1":
+        g, a = layouts.empty_layout(16, 4)
+        g, a = g[None].copy(), a[None].copy()
+    else:
+        g, a, _ = es.object_pool(spec, 1, 11)
+    env = BatchedMultiGridEnv(spec, B, DEV)
+    if not tracked:
+        env._tracks = lambda: False                          # (on the instance: its steps bind the untracked entry, mgx_step_ex)
+        split = env.split
+
+        def untracked_split(parts):                          # (... and so do the steps of its sub-shards, capture_steps' included)
+            children = split(parts)
+            for c in children:
+                c._tracks = env._tracks
+            return children
+        env.split = untracked_split
+    k = np.zeros(B, np.int64)
+    env.load_state(g[k], a[k], rng=rnglib.synthetic_words(B, 3, 0), step_count=(np.arange(B) % spec.max_steps).astype(np.int32))
+    env.set_layout_pool(g, a)
+    return env
+
+
+@pytest.mark.parametrize("seed", [1, 2])
+@pytest.mark.parametrize("form", es.BIG_FORMS)
+def test_the_size_that_reads_the_marker(form, seed):
+    B = THROUGHPUT
+    ops = es.make_ops(form, B, 40, seed, gpu=True, kinds=BIG_KINDS, weights=BIG_WEIGHTS, every_third=True)
+    env, twin = big_env(form, True), big_env(form, False)
+    assert env.backend.launch_info(B)["envs_per_wavefront"] * 2048 < B, "not the family of launches that reads the marker"
+    assert int((env._marker == 0).sum()) == B and int((twin._marker >= 0).sum()) == 0
+    ce, ct = es.new_ctx(), es.new_ctx()
+    edits_in_marked_envs = tracked_entry = 0
+    for i, op in enumerate(ops):
+        where = es.where_text(form, B, seed, i, ops)
+        if op["kind"] == "edit":                              # the negative control: the edit lands in marked envs, and shows
+            ids = torch.from_numpy(op["env_ids"]).to(DEV)
+            marked = env._marker[ids] >= 0
+            before = env.gen_obs()[0][ids].clone()
+            twin.gen_obs()
+        oe, ot = es.apply(env, op, ce), es.apply(twin, op, ct)
+        if op["kind"] == "edit":
+            after = env.gen_obs()[0][ids]
+            twin.gen_obs()
+            edits_in_marked_envs += int((marked & (before != after).flatten(1).any(dim=1)).sum())
+        es.invariants(env, where)
+        es.compare(env, twin, ce, ct, where, oe, ot, to_host=False)
+        ent, tent = env._bound.get((True, False)), twin._bound.get((True, False))
+        tracked_entry += int(bool(ent and ent[2]))
+        assert not (tent and tent[2]), "the twin's steps keep the marker: it is no reference"
+    assert tracked_entry > 0, "step(auto_reset=True) never ran through mgx_step_tracked"
+    assert edits_in_marked_envs > 0, "no cell edit landed in a marked env and changed what it observes"
+    assert sum(o["kind"] == "step" and o["auto_reset"] for o in ops) >= 13
