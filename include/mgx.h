@@ -793,6 +793,57 @@ typedef struct MgxEnvRows {
 int mgx_env_copy(const MgxSpec *spec, int64_t n, const MgxEnvRows *src, const int64_t *src_idx, const MgxEnvRows *dst,
                  const int64_t *dst_idx, int32_t *stage_tag, int32_t stage_mode, int32_t marker_fill, int32_t *bad, void *stream);
 
+/* STATE KEYS (additive to ABI 11): a 64-bit identity of an env's state, and of an agent's observation, made on the device in ONE
+ * launch that reads the state once -- a transposition key for a search over forked envs, a cell key for an archive of snapshots,
+ * the thing `torch.unique` counts for count-based exploration.  Build-defined: the reference has no such notion.
+ *
+ * THE RULE.  A key is the XOR of splitmix64(w ^ salt) over a set of 64-bit words w = tag << 60 | idx << 32 | payload (32-bit
+ * payload).  splitmix64(x): x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) *
+ * 0x94D049BB133111EB; return x ^ x >> 31 -- all mod 2^64; splitmix64(0) = 0xE220A8397B1DCDAF.  `salt` is the caller's (0 is as
+ * good as any); a second salt gives an independent second key to callers who want 128 bits.  Every (tag, idx) occurs once in a key,
+ * so no two terms cancel, and XOR makes the key independent of the order in which the words are visited.
+ *
+ * A STATE KEY covers
+ *   tag 1  cells       the cell at p = y * W + x as the triple (t, col, sb) that `BatchedMultiGridEnv.grid` shows for the spec's cell
+ *                      format (a box's content in the state byte included: "BOX CONTENTS"), c = (t & 15) | (col & 7) << 4 | sb << 8,
+ *                      16 bits; the derived opaque bit of the packed formats is NOT part of c.  Word j (idx = j) holds the cells 2j
+ *                      and 2j + 1: payload = c[2j] | c[2j + 1] << 16; with H * W odd the missing last cell is 0xFFFF.  At most
+ *                      32 513 words (255 x 255 cells): idx fits 16 bits;
+ *   tag 2  agents      for agent a and half h in {0, 1}: idx = 2a + h, payload = the little-endian u32 of bytes 4h .. 4h + 3 of the
+ *                      agent's 8-byte row;
+ *   tag 3  aux         idx 0..3, the little-endian u32s of the 16 aux bytes; a state set without `aux` is keyed as 16 zero bytes;
+ *   tag 4  step count  only with MGX_KEY_STEP_COUNT: idx 0, payload = (uint32_t)step_count;
+ *   tag 5  rng         only with MGX_KEY_RNG: idx 0..7, the little-endian u32 halves of the four PCG64 words.
+ * Engine state is never part of a key: the layout marker, the episode counter, the generator's words, the running episode.
+ * It follows that
+ *   * the same reference-visible state has the same key in all three cell formats (16-bit, compact, byte triples);
+ *   * byte-grid values outside the packed format (the ones `grid_bad` counts) are keyed after the masks above.
+ *
+ * An OBSERVATION KEY covers one agent view:
+ *   tag 8  image       idx = j over the ceil(3 * v * v / 4) little-endian u32s of the view's v * v * 3 image bytes, zero-padded at
+ *                      the tail;
+ *   tag 9  direction   idx 0, payload = dir.
+ * The agent's index is no part of it: two agents that see the same thing have the same key.
+ *
+ * mgx_state_key: keys[i] = the key of row src_idx[i] of the state set `src` (a NULL src_idx is the identity i; indices may repeat),
+ * i < n.  An index outside [0, rows) leaves keys[i] untouched and is counted as mgx_env_copy counts a bad pair: bad[0] += 1,
+ * bad[1] = min(bad[1], i); `bad` may be NULL.  Of `src` only cells, agents, step_count, rng (required) and aux (nullable) are read.
+ * Return codes: a bad spec (as mgx_env_copy), n < 0, NULL `src`, rows < 0, an unknown flag: MGX_ERR_INVALID_ARGUMENT; then n == 0:
+ * MGX_OK, nothing is launched; then a NULL required member or NULL `keys`, or a misaligned pointer -- 16 bytes for rng and aux, 8 for
+ * agents, `keys` and the index array, 4 for step_count and `bad`, 2 for 16-bit cells -- MGX_ERR_INVALID_ARGUMENT; more than INT_MAX
+ * workgroups, or more than 2^17 cells per env: MGX_ERR_UNSUPPORTED.
+ *
+ * mgx_obs_key: keys[i] = the key of view i of obs u8[n_views,v,v,3] (contiguous, any alignment) and dir u8[n_views], v =
+ * spec->view_size.  Return codes: NULL spec, n_views < 0, view_size outside 1..MGX_MAX_VIEW: MGX_ERR_INVALID_ARGUMENT; then
+ * n_views == 0: MGX_OK; then a NULL pointer or `keys` not 8-byte aligned: MGX_ERR_INVALID_ARGUMENT; more than INT_MAX workgroups:
+ * MGX_ERR_UNSUPPORTED. */
+enum { MGX_KEY_STEP_COUNT = 1, MGX_KEY_RNG = 2 };
+
+int mgx_state_key(const MgxSpec *spec, int64_t n, const MgxEnvRows *src, const int64_t *src_idx, uint32_t flags, uint64_t salt,
+                  int64_t *keys, int32_t *bad, void *stream);
+int mgx_obs_key(const MgxSpec *spec, int64_t n_views, const uint8_t *obs, const uint8_t *dir, uint64_t salt, int64_t *keys,
+                void *stream);
+
 #ifdef __cplusplus
 }
 #endif

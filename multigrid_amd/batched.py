@@ -131,6 +131,39 @@ class EnvSnapshot:
     def nbytes(self) -> int:
         return sum(t.numel() * t.element_size() for t in self.tensors.values())
 
+    def state_key(self, rows: torch.Tensor | None = None, *, salt: int = 0, step_count: bool = False, rng: bool = False,
+                  out: torch.Tensor | None = None) -> torch.Tensor:
+        """The keys of the snapshot rows `rows` (contiguous int64 [n] on the snapshot's device; None = every row, in order) -- the
+        launch of `BatchedMultiGridEnv.state_key()` over the snapshot's own tensors, through the backend of the env that took it: a
+        row's key is the key that env had when the snapshot was taken.  A row outside [0, rows) leaves its key as it was and is
+        reported by that env's `check_errors()`."""
+        env = self._env() if self._env is not None else None
+        if env is None:
+            raise RuntimeError("state_key: the env this snapshot was taken from is gone (its backend makes the launch)")
+        env.join()
+        n = self.rows if rows is None else int(env._index_arg("state_key", "rows", rows).shape[0])
+        flags, salt = _key_args("state_key", salt, step_count, rng)
+        keys = _key_out("state_key", out, (n,), self.device)
+        members = {m: self.tensors.get(m) for m in ("cells", "agents", "rng", "step_count", "aux")}
+        env.backend.state_key(n, members, self.rows, rows, flags, salt, keys, env._bad_words())
+        return keys
+
+
+def _key_args(what: str, salt, step_count, rng) -> tuple:
+    """(flags, salt) of mgx_state_key / mgx_obs_key"""
+    if isinstance(salt, bool) or not isinstance(salt, int) or not 0 <= salt < 2 ** 64:
+        raise ValueError(f"{what}: salt must be an int in [0, 2**64)")
+    return (_lib.KEY_STEP_COUNT if step_count else 0) | (_lib.KEY_RNG if rng else 0), salt
+
+
+def _key_out(what: str, out, shape: tuple, device) -> torch.Tensor:
+    if out is None:
+        return torch.zeros(shape, dtype=torch.int64, device=device)
+    if not torch.is_tensor(out) or out.dtype is not torch.int64 or tuple(out.shape) != tuple(shape) or out.device != device \
+            or not out.is_contiguous():
+        raise ValueError(f"{what}: out= must be a contiguous int64 tensor of shape {tuple(shape)} on {device}")
+    return out
+
 
 class PersistentSession:
     """Closed-loop stepping without a kernel boundary per step (include/mgx.h: mgx_step_persistent): ONE launch of the step kernel
@@ -1285,9 +1318,14 @@ class BatchedMultiGridEnv:
         self._need_state()
         if self._parent is not None:
             raise RuntimeError(f"{what}: this env is a sub-shard of split() -- a view of its parent's tensors; {what} on the parent")
+        self._bad_words()
+        self.join()
+
+    def _bad_words(self) -> torch.Tensor:
+        """i32[2] on the device: how many pairs / keys the copy and key kernels skipped for an index out of range, and the first"""
         if self._copy_bad is None:
             self._copy_bad = torch.tensor([0, INT32_MAX], dtype=torch.int32).to(self.device)
-        self.join()
+        return self._copy_bad
 
     def _index_arg(self, what: str, name: str, t, check_below=None, distinct: bool = False):
         if not torch.is_tensor(t) or t.dtype is not torch.int64 or t.dim() != 1 or t.device != self._cells.device \
@@ -1395,6 +1433,57 @@ class BatchedMultiGridEnv:
         if src_ids.shape[0] != dst_ids.shape[0]:
             raise ValueError(f"fork: {int(src_ids.shape[0])} source(s) for {int(dst_ids.shape[0])} destination(s)")
         self.restore(self.snapshot(src_ids), dst_ids, check=check)
+
+    # ------------------------------------------------------------------------------------------ state / observation keys
+    def state_key(self, env_ids: torch.Tensor | None = None, *, salt: int = 0, step_count: bool = False, rng: bool = False,
+                  out: torch.Tensor | None = None) -> torch.Tensor:
+        """A 64-bit key of the state of the envs `env_ids` (include/mgx.h "STATE KEYS"): int64 [n] on the device, made by ONE launch
+        (mgx_state_key) on the current stream that reads the state once -- no host round trip, no synchronisation, capturable in a
+        graph.  Equal states have equal keys; different ones differ but for a 2^-64 chance, so `torch.unique(keys)` dedups forked
+        envs, a sort counts visits, and a search has its transposition key.
+
+        The key covers what the reference shows of an env -- the grid (as `.grid` shows it, a box's content included), the agent
+        rows and the hook state `aux` -- and, on request, `step_count` and np_random (`rng`).  It does not depend on the cell format
+        (an env on 16-bit cells and one on compact cells in the same state have the same key), and never on engine state: the
+        layout marker, the episode counter, the generator's words, the running episode.
+
+        env_ids  a contiguous int64 [n] tensor on the env's device (None = every env, in order), read by the kernel as it is; ids
+                 may repeat.  An id outside [0, batch) leaves its key as it was and is reported by `check_errors()`.
+        salt     any int in [0, 2**64): another salt gives an independent key (two of them: 128 bits)
+        out      an int64 [n] tensor on the env's device to write: a caller that keys every step allocates nothing."""
+        self._copy_entry("state_key")
+        n = self.batch if env_ids is None else int(self._index_arg("state_key", "env_ids", env_ids).shape[0])
+        flags, salt = _key_args("state_key", salt, step_count, rng)
+        keys = _key_out("state_key", out, (n,), self._cells.device)
+        # (`_cells`, not `cells`: reading the grid keeps the layout marker's promises)
+        rows = {"cells": self._cells, "agents": self.agents, "rng": self.rng, "step_count": self.step_count, "aux": self.aux}
+        self.backend.state_key(n, rows, self.batch, env_ids, flags, salt, keys, self._copy_bad)
+        return keys
+
+    def obs_key(self, obs: torch.Tensor | None = None, dir: torch.Tensor | None = None, *, salt: int = 0,
+                out: torch.Tensor | None = None) -> torch.Tensor:
+        """A 64-bit key per agent observation (include/mgx.h "STATE KEYS": the view's image bytes and its direction; the agent's
+        index is no part of it), by ONE launch (mgx_obs_key) on the current stream.  Default: the env's own `obs` / `dir` of the last
+        step or gen_obs -> int64 [B, A].  Otherwise any contiguous uint8 [..., v, v, 3] with a matching uint8 [...] on the env's
+        device -- a rollout's [T, B, A, ...] outputs -- and the result has the leading shape.  `salt`, `out` as in `state_key()`.  The
+        default needs a loaded state and no open persistent session (pass a session's outputs explicitly)."""
+        if (obs is None) != (dir is None):
+            raise ValueError("obs_key: pass both obs and dir, or neither")
+        v, dev = self.spec.view_size, self._cells.device
+        if obs is None:                  # (the env's own outputs: there are none before a state is loaded)
+            self._need_state()
+            obs, dir = self.obs, self.dir
+        for name, t in (("obs", obs), ("dir", dir)):
+            if not torch.is_tensor(t) or t.dtype is not torch.uint8 or t.device != dev or not t.is_contiguous():
+                raise ValueError(f"obs_key: {name} must be a contiguous uint8 tensor on {dev}")
+        if obs.dim() < 3 or tuple(obs.shape[-3:]) != (v, v, 3) or tuple(obs.shape[:-3]) != tuple(dir.shape):
+            raise ValueError(f"obs_key: obs must have shape [..., {v}, {v}, 3] and dir the leading shape [...], got "
+                             f"{tuple(obs.shape)} and {tuple(dir.shape)}")
+        _, salt = _key_args("obs_key", salt, False, False)
+        keys = _key_out("obs_key", out, tuple(dir.shape), dev)
+        self.join()
+        self.backend.obs_key(int(dir.numel()), obs, dir, salt, keys)
+        return keys
 
     def outputs_to_host(self) -> dict:
         """Everything the last step / gen_obs handed back, on the host after ONE device-to-host copy (into a pinned buffer) and one

@@ -9,7 +9,8 @@ stored beside the library (`<lib>.srchash`); a tree copied with fresh or stale m
 silently reuses a library built from other sources.
 
 `--debug-knobs` builds lib/libmgx_dbg.so with -DMGX_DEBUG_KNOBS=1: the profiling tools' variant that also exports
-mgx_debug_skip_phases / mgx_debug_set_envs_per_wavefront / mgx_debug_set_waves_per_workgroup.  The product library
+mgx_debug_skip_phases / mgx_debug_set_envs_per_wavefront / mgx_debug_set_waves_per_workgroup (and, for
+tools/state_key_bench.py, mgx_debug_obs_key_bytes / mgx_debug_stream_read).  The product library
 never has them; `MGX_LIBMGX=<path>` makes multigrid_amd load another build and bench.py then marks its line invalid.
 """
 from __future__ import annotations
@@ -28,11 +29,12 @@ VIEWS = (3, 5, 7, 9, 11, 13, 15)
 #: that the units compile in parallel (a single unit took a minute).
 UNITS = ([("mgx_kernels", os.path.join(CSRC, "mgx_kernels.hip"), ()), ("mgx_aux", os.path.join(CSRC, "mgx_aux.hip"), ()),
           ("mgx_layout_gen", os.path.join(CSRC, "mgx_layout_gen.hip"), ()), ("mgx_render", os.path.join(CSRC, "mgx_render.hip"), ()),
-          ("mgx_stats", os.path.join(CSRC, "mgx_stats.hip"), ()), ("mgx_env_copy", os.path.join(CSRC, "mgx_env_copy.hip"), ())]
+          ("mgx_stats", os.path.join(CSRC, "mgx_stats.hip"), ()), ("mgx_env_copy", os.path.join(CSRC, "mgx_env_copy.hip"), ()),
+          ("mgx_state_key", os.path.join(CSRC, "mgx_state_key.hip"), ())]
          + [(f"mgx_fused_v{v}", os.path.join(CSRC, "mgx_fused_inst.hip"), (f"MGX_INST_V={v}",)) for v in VIEWS])
 SRCS = sorted({u[1] for u in UNITS})
 DEPS = SRCS + [os.path.join(CSRC, "mgx_aux_geom.h"), os.path.join(CSRC, "mgx_fused.h"), os.path.join(CSRC, "mgx_fused_body.inc"), os.path.join(CSRC, "mgx_host.h"), os.path.join(CSRC, "mgx_layout_gen.h"), os.path.join(CSRC, "mgx_rules.h"),
-               os.path.join(CSRC, "mgx_render.h"), os.path.join(ROOT, "include", "mgx.h")]
+               os.path.join(CSRC, "mgx_render.h"), os.path.join(CSRC, "mgx_state_key.h"), os.path.join(ROOT, "include", "mgx.h")]
 LIB = os.path.join(HERE, "lib", "libmgx.so")
 LIB_DBG = os.path.join(HERE, "lib", "libmgx_dbg.so")
 LIB_CHK = os.path.join(HERE, "lib", "libmgx_chk.so")

@@ -103,6 +103,41 @@ inline EnvCopyGeom env_copy_geom(int tile_bytes, int64_t n) {
     return g;
 }
 
+// state_key (mgx_state_key.hip): a wavefront owns the `run` consecutive envs env_copy_geom gives it, and every env of them a GROUP of
+// lanes -- the largest power of two with group * run <= 64 (one lane per env at run = 64, the whole wavefront at run = 1).  Lane k of
+// a group takes the env's chunks k, k + group, ...; a chunk is what one load covers -- `unit` bytes, but at least one key word (two
+// cells), which a unit below that loads in pieces: 2 * cb bytes for 1- and 2-byte cells, 6 for byte triples.
+struct StateKeyGeom {
+    int run, group;         // envs per wavefront; lanes per env (a power of two)
+    int64_t nwaves, blocks;
+};
+
+inline StateKeyGeom state_key_geom(int tile_bytes, int64_t n) {
+    const EnvCopyGeom c = env_copy_geom(tile_bytes, n);
+    StateKeyGeom g;
+    g.run = c.run; g.nwaves = c.nwaves; g.blocks = c.blocks;
+    g.group = 64;
+    while (g.group * g.run > 64) g.group >>= 1;
+    return g;
+}
+
+// the load unit of the cells: the widest of 16, 8, 4, 2, 1 bytes that divides the tile size and the base address; byte triples are
+// read in units of at most 2 (a key word of theirs is 6 bytes)
+inline int state_key_unit(int cb, int tile_bytes, uintptr_t cells) {
+    const int unit = env_copy_unit(tile_bytes, cells, cells).unit;
+    return cb == 3 && unit > 2 ? 2 : unit;
+}
+inline int state_key_chunk_bytes(int cb, int unit) { return cb == 3 ? 6 : (unit > 2 * cb ? unit : 2 * cb); }
+
+// obs_key: a view of 3 * v * v bytes is ceil(3 * v * v / 4) words; its lane group is the smallest power of two that leaves a lane at
+// most four of them (2 lanes at v = 3, 16 at v = 7, 64 at v = 15), a wavefront takes 64 / group views
+inline int obs_key_group(int view_bytes) {
+    const int words = (view_bytes + 3) / 4;
+    int g = 1;
+    while (g < 64 && 4 * g < words) g <<= 1;
+    return g;
+}
+
 // persistent stepping: granules (4 action bytes each) per env and in all, and the reciprocal the producer kernels find a granule's
 // env with -- g / gpe by recip32, so the batch ends where that stops being exact (recip32_exact_below: 2^30 granules at gpe = 5,
 // 1 431 655 766 at gpe = 7, beyond 2^31 at every other gpe <= 8) or at 2^31 granules, whichever comes first

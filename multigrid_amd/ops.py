@@ -542,5 +542,24 @@ class HipBackend:
                                          stage_mode, int(bool(marker_fill)), _ptr(bad), _stream(dev))
         _lib.check(rc, "mgx_env_copy")
 
+    # ------------------------------------------------------------------------------------------ state / observation keys
+    def state_key(self, n, rows, n_rows, idx, flags, salt, keys, bad):
+        """mgx_state_key on torch's current stream: keys[i] (i64[n]) = the key of row idx[i] of the state set `rows` (a dict of
+        tensors holding `n_rows` rows; idx: i64[n] on the device, None = the identity, read by the kernel as it is).  `flags`:
+        _lib.KEY_STEP_COUNT | _lib.KEY_RNG; `salt`: an int in [0, 2**64); `bad` i32[2] or None."""
+        s = self._env_rows(rows, n_rows)
+        dev = keys.device
+        with torch.cuda.device(dev):
+            rc = _lib.lib().mgx_state_key(C.byref(self.sc), n, C.byref(s), _ptr(idx), flags, salt, keys.data_ptr(), _ptr(bad),
+                                          _stream(dev))
+        _lib.check(rc, "mgx_state_key")
+
+    def obs_key(self, n, obs, dir, salt, keys):
+        """mgx_obs_key on torch's current stream: keys[i] (i64[n]) = the key of view i of obs u8[n,v,v,3] / dir u8[n]."""
+        dev = keys.device
+        with torch.cuda.device(dev):
+            rc = _lib.lib().mgx_obs_key(C.byref(self.sc), n, obs.data_ptr(), dir.data_ptr(), salt, keys.data_ptr(), _stream(dev))
+        _lib.check(rc, "mgx_obs_key")
+
     def launch_info(self, B) -> dict:
         return _lib.launch_info(self.spec, B)
