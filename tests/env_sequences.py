@@ -18,7 +18,7 @@ from multigrid_amd import BatchedMultiGridEnv, EnvSpec, _lib, layouts
 from oracle import binding as ob
 from tests import util
 from tests.test_env_snapshot import TRIO, CopyOracle
-from tests.test_episode_stats import empty_pool, model_restart, model_stats, new_state
+from tests.test_episode_stats import model_restart, model_stats, new_state
 
 NONE, BEFORE, AFTER = _lib.RESTART_NONE, _lib.RESTART_BEFORE, _lib.RESTART_AFTER
 STATE = ("_cells", "agents", "rng", "step_count")
@@ -26,7 +26,13 @@ OUTPUTS = ("obs", "dir", "reward", "terminated", "truncated")
 FORMS = ("plain", "pool1", "pool4_objects", "pool_compact", "gen", "gen_candidates", "gen_between", "bup_candidates")
 #: the batch whose launches READ the layout marker (more than 2048 wavefronts, one layout): tests/test_env_sequences_gpu.py
 BIG_FORMS = ("big_empty1", "big_objects1")
-POOL_FORMS = ("pool1", "pool4_objects", "pool_compact") + BIG_FORMS
+#: `plain` and `pool1` on shapes of their own -- grids that are not square --, which the HIP env steps on a kernel compiled at run time
+#: (make_env(specialise=True); a registration serves every env of its geometry for the rest of the process: no other form, and no
+#: other test file, uses these shapes): tests/test_jit_forms_gpu.py
+JIT_FORMS = ("plain_jit", "pool1_jit")
+PLAIN_FORMS = ("plain", "plain_jit")                         # no restart source: load_state alone
+POOL1_FORMS = ("pool1", "pool1_jit")
+POOL_FORMS = ("pool1", "pool4_objects", "pool_compact") + BIG_FORMS + ("pool1_jit",)
 GEN_FORMS = ("gen", "gen_candidates", "gen_between", "bup_candidates")
 SPECS = {
     "plain": EnvSpec(8, 8, 3, 5, max_steps=12),
@@ -39,10 +45,13 @@ SPECS = {
     "bup_candidates": EnvSpec(11, 6, 2, 7, max_steps=8, joint_reward=True, env_kind="blockedunlockpickup"),
     "big_empty1": EnvSpec(16, 16, 4, 7, max_steps=8),
     "big_objects1": EnvSpec(16, 16, 4, 7, max_steps=8),
+    "plain_jit": EnvSpec(7, 6, 3, 5, max_steps=12),
+    "pool1_jit": EnvSpec(6, 5, 2, 3, max_steps=6),
 }
 FIRST_ENV = {"pool4_objects": 11, "gen_between": 11, "bup_candidates": 11}
 #: the pool sizes a form alternates between when `pool_replace` gives it another K
-POOL_K = {"pool1": (1, 2), "pool4_objects": (4, 3), "pool_compact": (2, 3), "big_empty1": (1, 2), "big_objects1": (1, 2)}
+POOL_K = {"pool1": (1, 2), "pool4_objects": (4, 3), "pool_compact": (2, 3), "big_empty1": (1, 2), "big_objects1": (1, 2),
+          "pool1_jit": (1, 2)}
 #: (type, color, state) triples a cell edit writes: every cell format holds them, and an agent may stand on each (the edit may land
 #: under one): empty, floors, lava, a goal
 EDIT_CELLS = np.array([[1, 0, 0], [3, 3, 0], [3, 1, 0], [9, 0, 0], [8, 1, 0], [3, 4, 0]], np.uint8)
@@ -168,16 +177,38 @@ def object_pool(spec, K, seed):
     return st["grid"], st["agents"], None
 
 
+def empty_start(spec, pos=(1, 1), direction=0):
+    """layouts.empty_layout for a grid that may be wider than high: the square layout's upper rows, closed by a wall, the goal in
+    the new far corner"""
+    W, H = spec.width, spec.height
+    g, a = layouts.empty_layout(W, spec.num_agents, agent_start_pos=pos, agent_start_dir=direction)
+    if H != W:
+        assert H < W and pos[1] < H - 1
+        wall, goal, empty = g[0, 0].copy(), g[W - 2, W - 2].copy(), g[1, 1].copy()
+        g[W - 2, W - 2] = empty
+        g = g[:H].copy()
+        g[H - 1] = wall
+        g[H - 2, W - 2] = goal
+    return g, a
+
+
+def start_pool(spec):
+    """test_episode_stats.empty_pool for any such grid: the reference's start, and one cell before the goal, facing it"""
+    g0, a0 = empty_start(spec)
+    g1, a1 = empty_start(spec, (spec.width - 3, spec.height - 2), 0)
+    return np.stack([g0, g1]), np.stack([a0, a1])
+
+
 def small_pool(spec, K, r):
-    """K starts of a 5x5 Empty grid with one more object on it: the layouts differ in their CELLS (the two of
+    """K starts of a small Empty grid with one more object on it: the layouts differ in their CELLS (the two of
     test_episode_stats.empty_pool differ in the agents only); some starts face the goal"""
     gs, ags = [], []
     for _ in range(K):
         pos = [(1, 1), (2, 3), (3, 2), (2, 2)][int(r.integers(0, 4))]
-        g, a = layouts.empty_layout(spec.width, spec.num_agents, agent_start_pos=pos, agent_start_dir=int(r.integers(0, 4)))
+        g, a = empty_start(spec, pos, int(r.integers(0, 4)))
         while True:
             x, y = (int(v) for v in r.integers(1, spec.width - 1, size=2))
-            if (x, y) != pos and (x, y) != (spec.width - 2, spec.height - 2):
+            if (x, y) != pos and (x, y) != (spec.width - 2, spec.height - 2) and y < spec.height - 1:
                 break
         g[y, x] = POOL_OBJECTS[int(r.integers(0, 3))]
         gs.append(g); ags.append(a)
@@ -191,8 +222,9 @@ def pool_content(form, K, r):
     return small_pool(SPECS[form], K, r)
 
 
-def make_env(form, B, device="cpu", backend=None):
-    """One env of `form`; on the CPU over a SeqOracle (or `backend`), on a HIP device over the product's launcher."""
+def make_env(form, B, device="cpu", backend=None, specialise=False):
+    """One env of `form`; on the CPU over a SeqOracle (or `backend`), on a HIP device over the product's launcher.
+    specialise: a HIP env steps on a kernel compiled for its shape at run time (env.specialise()); an oracle-backed one is as ever."""
     spec = SPECS[form]
     kw = {}
     if torch.device(device).type == "cpu":
@@ -200,15 +232,17 @@ def make_env(form, B, device="cpu", backend=None):
     env = BatchedMultiGridEnv(spec, B, device, first_env=FIRST_ENV.get(form, 0), **kw)
     if isinstance(env.backend, SeqOracle):
         env.backend.attach(env)
-    if form == "plain":
+    if specialise and is_hip(env):
+        env.specialise()
+    if form in PLAIN_FORMS:
         st = util.random_state(spec, B, seed=7)
         env.load_state(st["grid"], st["agents"], st["rng"], None, st["step_count"])
-    elif form == "pool1":
-        pg, pa = empty_pool(spec)
+    elif form in POOL1_FORMS:
+        pg, pa = start_pool(spec)
         env.set_layout_pool(pg[1:2], pa[1:2])              # (one cell before the goal, facing it: both kinds of episode end)
         env.reset(seed=3)
     elif form == "pool_compact":
-        pg, pa = empty_pool(spec)
+        pg, pa = start_pool(spec)
         env.set_layout_pool(pg, pa)
         env.reset(seed=3)
     elif form == "pool4_objects":
@@ -233,7 +267,7 @@ def legal_kinds(form, B, gpu):
     """every kind `form` can meet at batch B (what the census asks for)"""
     kinds = ["step", "rollout", "snapshot", "snapshot_out", "restore", "fork", "edit", "load_state_dict", "track", "reset_totals",
              "stats_lsd", "seed", "gen_obs", "full_obs", "one_hot_obs", "step_one_hot"]
-    if form != "plain":
+    if form not in PLAIN_FORMS:
         kinds += ["reset_done", "reset"]
     if form in POOL_FORMS:
         kinds += ["pool_refill", "pool_replace"]
@@ -241,7 +275,7 @@ def legal_kinds(form, B, gpu):
         kinds.append("split")
     if gpu:
         kinds += ["capture_replay", "graph_again"]
-        if form in POOL_FORMS or form == "plain":
+        if form in POOL_FORMS or form in PLAIN_FORMS:
             kinds.append("persistent")
         if B >= 128:
             kinds.append("step_chains")
@@ -255,10 +289,10 @@ def make_ops(form, B, n_ops, seed, gpu=False, stretch=None, weights=None, kinds=
     stretch      (s, e): call s is `tm_begin` (a snapshot of the whole batch, the kept ones forgotten), and the calls s+1 .. e-1 are
                  PURE_KINDS that use only snapshots taken after s -- what the time machine records, restores and repeats
     kinds        restrict the kinds drawn (the large-batch test); every_third: that call at every third index instead of a draw"""
-    r = np.random.default_rng([seed, B, (FORMS + BIG_FORMS).index(form)])
+    r = np.random.default_rng([seed, B, (FORMS + BIG_FORMS + JIT_FORMS).index(form)])
     spec = SPECS[form]
     A, H, W = spec.num_agents, spec.height, spec.width
-    source = form != "plain"
+    source = form not in PLAIN_FORMS
     w = dict(WEIGHTS, **(weights or {}))
     allowed = set(legal_kinds(form, B, gpu)) if kinds is None else set(kinds)
     S = {"tracking": None, "snaps": {}, "graphs": {}, "version": 0, "persistent": 0, "K": POOL_K.get(form, (0,))[0], "next_slot": 0,
@@ -285,7 +319,7 @@ def make_ops(form, B, n_ops, seed, gpu=False, stretch=None, weights=None, kinds=
         if kind in ("step", "step_chains"):
             op.update(acts=actions(), auto_reset=auto())
         elif kind == "step_one_hot":
-            op.update(acts=actions(), auto_reset=bool(form in ("pool1", "pool4_objects") and r.random() < 0.5))
+            op.update(acts=actions(), auto_reset=bool(form in POOL1_FORMS + ("pool4_objects",) and r.random() < 0.5))
         elif kind == "rollout":
             op.update(acts=actions(int(r.integers(1, 5))), auto_reset=auto())
         elif kind == "reset":
@@ -696,7 +730,7 @@ def assert_census(c, form, B, gpu=False):
         need = 1 if k in GPU_KINDS else 3
         assert c.get(k, 0) >= need, f"form {form}: call kind {k} ran {c.get(k, 0)} time(s), {need} needed: {c}"
     need = ["restore_with_repeated_rows", "tracking_on_off_on", "restored_row_without_the_running_episode"]
-    if form != "plain":                                       # (no restart source: a finished env stays finished)
+    if form not in PLAIN_FORMS:                               # (no restart source: a finished env stays finished)
         need += ["restart_by_truncation", "restored_env_crossed_an_episode_end"]
         if form != "bup_candidates":                          # (the box behind the locked door: no random walk of 8 steps picks it up)
             need.append("restart_by_termination")

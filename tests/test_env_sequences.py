@@ -4,7 +4,8 @@ Every feature of batched.py that keeps engine state beside the public state -- t
 generator's slots, reset(seed, mask), the episode accounting, snapshot / restore / fork -- has a suite of its own that walks a script
 written for it.  Here the calls come in arbitrary order:
 
-  * sequences: per form three seeds of 120 calls at 130 envs and one at 7.  After every call the layout marker's two rules hold
+  * sequences: per form (the two of es.JIT_FORMS included: on the oracle they are `plain` and `pool1` on grids that are not square)
+    three seeds of 120 calls at 130 envs and one at 7.  After every call the layout marker's two rules hold
     (env_sequences.invariants), EpisodeStats equals what the launches' own outputs make of it (SeqOracle.shadow: the accounting
     launch follows every stepping and restart form), and a second env given the same list holds the same bytes;
   * census: over a form's seeds every legal call kind ran at least three times, and the restarts, restores and switches that the
@@ -43,14 +44,14 @@ def sequence(form, B, seed):
 
 
 @pytest.mark.parametrize("B,seed", SEQUENCES)
-@pytest.mark.parametrize("form", es.FORMS)
+@pytest.mark.parametrize("form", es.FORMS + es.JIT_FORMS)
 def test_a_sequence_keeps_the_invariants_and_repeats(form, B, seed):
     ops, be = sequence(form, B, seed)
     assert len(ops) == N_OPS
     assert not set(o["kind"] for o in ops) & set(es.GPU_KINDS)
 
 
-@pytest.mark.parametrize("form", es.FORMS)
+@pytest.mark.parametrize("form", es.FORMS + es.JIT_FORMS)
 def test_census(form):
     runs = [sequence(form, B, seed) for B, seed in SEQUENCES]
     c = es.census_of([r[0] for r in runs], [r[1] for r in runs])
@@ -98,7 +99,7 @@ def time_machine(form, B, seed, device="cpu", gpu=False):
     return ops[s + 1:]
 
 
-@pytest.mark.parametrize("form", es.FORMS)
+@pytest.mark.parametrize("form", es.FORMS + es.JIT_FORMS)
 def test_time_machine(form):
     kinds = {o["kind"] for o in time_machine(form, 130, 5)}
     assert kinds <= set(es.PURE_KINDS) and "step" in kinds and "restore" in kinds

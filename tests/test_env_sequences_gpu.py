@@ -8,14 +8,15 @@ oracle-backed envs: tests/test_env_sequences.py).
   * the size that READS the layout marker: 32 784 envs (more than 2048 wavefronts) on a one-layout pool, against a second HIP env whose
     steps are bound untracked (`_tracks` replaced on the instance): every third call a step(auto_reset=True) that would trust a
     stale marker, cell edits that land in marked envs and change what they observe;
-  * the pinned cases of the CPU file against the oracle."""
+  * the pinned cases of the CPU file against the oracle;
+  * the forms `plain_jit` and `pool1_jit`: one list each on a HIP env whose step kernel is compiled at run time and registered."""
 import functools
 
 import numpy as np
 import pytest
 import torch
 
-from multigrid_amd import BatchedMultiGridEnv, layouts, rng as rnglib
+from multigrid_amd import BatchedMultiGridEnv, jit, layouts, rng as rnglib
 from tests import env_sequences as es
 from tests.test_env_sequences import time_machine
 from tests.test_grid_layout_marker import THROUGHPUT
@@ -43,9 +44,11 @@ def live_slots(env, op) -> int:
 @functools.lru_cache(maxsize=None)
 def sequence(form, B, seed):
     ops = es.make_ops(form, B, N_OPS, seed, gpu=True)
-    hip, twin = es.make_env(form, B, DEV), es.make_env(form, B)
+    jit_form = form in es.JIT_FORMS                           # (the HIP env steps on a kernel compiled for its shape at run time)
+    hip, twin = es.make_env(form, B, DEV, specialise=jit_form), es.make_env(form, B, specialise=jit_form)
     ch, ct = es.new_ctx(), es.new_ctx()
-    seen = {"live_slots": 0, "tracked_entry": False}
+    seen = {"live_slots": 0, "tracked_entry": False, "shape_kernel": (hip.shape_kernel, twin.shape_kernel),
+            "fixed_shape": hip.backend.launch_info(B)["fixed_shape"]}
     for i, op in enumerate(ops):
         where = es.where_text(form, B, seed, i, ops)
         seen["live_slots"] += live_slots(hip, op)
@@ -64,6 +67,19 @@ def sequence(form, B, seed):
 def test_hip_equals_the_oracle_after_every_call(form, B, seed):
     ops, be, seen = sequence(form, B, seed)
     assert len(ops) == N_OPS
+
+
+@pytest.mark.skipif(not jit.hiprtc_available(), reason="no libhiprtc")
+@pytest.mark.parametrize("form", es.JIT_FORMS)
+def test_a_registered_shape_equals_the_oracle_after_every_call(form):
+    """`plain` and `pool1` on shapes whose kernel is compiled at run time and registered (tests/test_jit_forms_gpu.py has the other
+    forms such a kernel serves): every step of the list without a one-hot output, its auto-reset steps included, runs it."""
+    ops, be, seen = sequence(form, 130, 1)
+    assert len(ops) == N_OPS
+    assert seen["shape_kernel"][0] in ("compiled", "registered") and seen["shape_kernel"][1] is None
+    assert seen["fixed_shape"] == 100, "the launches of this batch do not run the registered kernel"      # MGX_SHAPE_RUNTIME_COMPILED
+    assert sum(o["kind"] == "step" for o in ops) >= 3
+    assert any(o["kind"] == "step" and o["auto_reset"] for o in ops) == (form == "pool1_jit")
 
 
 @pytest.mark.parametrize("form", es.FORMS)

@@ -23,9 +23,10 @@ from tests import util
 from tests.test_reset_select import SelectOracle
 
 DEV = "cuda:0"
-STATE = ("_cells", "agents", "rng", "step_count", "episode")
+STATE = ("_cells", "agents", "rng", "step_count", "aux", "episode")
 OUT = ("obs", "dir", "reward", "terminated", "truncated", "was_reset")
-THROUGHPUT = 32784           # 2049 wavefronts of 16 envs: the smallest batch of the family that reads the marker
+THROUGHPUT = 32784           # 2049 wavefronts of 16 envs: the family that reads the marker, at this shape's full envs per wavefront
+#                              (the other grid sizes that qualify, and the batches just outside: tests/test_marker_sizes_gpu.py)
 
 
 def spec16(max_steps=8):
@@ -43,27 +44,34 @@ def object_pool(K, seed=11):
     return st["grid"], st["agents"]
 
 
-def make_env(spec, B, pool, device=DEV, backend=None, seed=3):
-    g, a = pool
-    k = np.arange(B) % g.shape[0]                          # the layout the pool gives env b in episode 0
-    env = BatchedMultiGridEnv(spec, B, device, backend=backend)
-    env.load_state(g[k], a[k], rng=rnglib.synthetic_words(B, seed, 0), step_count=(np.arange(B) % spec.max_steps).astype(np.int32))
-    env.set_layout_pool(g, a)
+def make_env(spec, B, pool, device=DEV, backend=None, seed=3, rows=None):
+    """B envs on the layouts of `pool` = (grids, agents[, auxs]), env b on layout b % K, with staggered step counts; rows=(lo, hi):
+    only the envs lo .. hi-1 of that batch (a slice for the oracle: the kernels are data-parallel over envs)"""
+    g, a = pool[0], pool[1]
+    x = pool[2] if len(pool) > 2 else None
+    lo, hi = rows if rows is not None else (0, B)
+    b = np.arange(lo, hi)
+    k = b % g.shape[0]                                     # the layout the pool gives env b in episode 0
+    env = BatchedMultiGridEnv(spec, hi - lo, device, first_env=lo, backend=backend)
+    env.load_state(g[k], a[k], rng=rnglib.synthetic_words(hi - lo, seed, lo), aux=None if x is None else x[k],
+                   step_count=(b % spec.max_steps).astype(np.int32))
+    env.set_layout_pool(g, a, x)
     return env
 
 
 def untracked_stepper(env):
     """env's step with auto-reset through mgx_step_ex: the same launcher, bound without the marker"""
-    f = env.backend.bind_step(env.batch, env._cells, env.agents, env.rng, env.step_count, None, env.err, env.obs, env.dir,
-                              env.reward, env.terminated, env.truncated, auto_reset=env._auto_reset_args(True, env.was_reset))
+    f = env.backend.bind_step(env.batch, env._cells, env.agents, env.rng, env.step_count, env.aux if env.spec.env_kind != "empty" else None,
+                              env.err, env.obs, env.dir, env.reward, env.terminated, env.truncated,
+                              auto_reset=env._auto_reset_args(True, env.was_reset))
     assert not f.tracked
     return f
 
 
-def actions(T, B, seed=5):
+def actions(T, B, seed=5, A=4):
     g = torch.Generator(device=DEV)
     g.manual_seed(seed)
-    return torch.randint(0, 7, (T, B, 4), dtype=torch.int8, device=DEV, generator=g)
+    return torch.randint(0, 7, (T, B, A), dtype=torch.int8, device=DEV, generator=g)
 
 
 def assert_same(e1, e2, ctx):

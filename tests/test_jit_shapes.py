@@ -40,7 +40,18 @@ def test_hiprtc_compiles_the_kernel_without_a_gpu(tmp_path):
     notes = subprocess.check_output(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--notes", str(p)], text=True)
     assert ".name:           mgx_jit_step\n" in notes and "mgx_jit_step_ar" in notes
     assert notes.count(".private_segment_fixed_size: 0") == 2 and notes.count(".vgpr_spill_count: 0") == 2
-
+    # the THROUGHPUT key (ensure_shape(latency_only=False)): no LDS-DMA tile loads, so its auto-reset kernel also holds the layout
+    # marker's read (MARK_RD) -- the smallest batch of more than 2048 wavefronts
+    from tests.marker_sizes import smallest_reading_batch
+    spec = mg.spec_for("MultiGrid-Empty-8x8-v0", agents=2)
+    key = jit.shape_key(spec, smallest_reading_batch(spec))
+    assert (key.dma, key.stream, key.built_in, key.envs_per_wavefront) == (0, 0, 0, 8)
+    assert "#define MGX_JIT_SHAPE 8, 8, 2, 8, false, 7, false, false" in jit.source_for(key)
+    p.write_bytes(jit.compile_shape(key))
+    notes = subprocess.check_output(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--notes", str(p)], text=True)
+    assert ".name:           mgx_jit_step\n" in notes and ".name:           mgx_jit_step_ar\n" in notes
+    assert notes.count(".private_segment_fixed_size: 0") == 2 and notes.count(".vgpr_spill_count: 0") == 2
+    assert notes.count(".sgpr_spill_count: 0") == 2
 
 CASES = [("MultiGrid-Empty-8x8-v0", dict(agents=2), 4096), ("MultiGrid-RedBlueDoors-8x8-v0", dict(agents=2), 4096),
          ("MultiGrid-Empty-Random-6x6-v0", dict(agents=3), 2048), ("MultiGrid-LockedHallway-4Rooms-v0", dict(agents=2), 1000)]
