@@ -844,6 +844,50 @@ int mgx_state_key(const MgxSpec *spec, int64_t n, const MgxEnvRows *src, const i
 int mgx_obs_key(const MgxSpec *spec, int64_t n_views, const uint8_t *obs, const uint8_t *dir, uint64_t salt, int64_t *keys,
                 void *stream);
 
+/* ACTION MASKS (additive to ABI 11): which of the 7 actions of an agent can do anything in the state it is in, for chosen rows of a
+ * state set, made on the device in ONE launch -- what a tree search needs before it forks one child per action, and what invalid-
+ * action masking wants next to the observation.  Build-defined: the reference has no such notion.
+ *
+ * THE RULE.  A mask is one byte per agent: bit k stands for action k (left 0, right 1, forward 2, pickup 3, drop 4, toggle 5,
+ * done 6: multigrid/core/actions.py:5-15); bit 6 and bit 7 are always 0.  For agent row r of an env, with (fx, fy) its front position
+ * (position + DIR_TO_VEC[dir]) and c the front cell as `BatchedMultiGridEnv.grid` shows it:
+ *   terminated  a terminated agent has mask 0;
+ *   turns       bits 0 and 1 are set for every agent that is not terminated;
+ *   outside     if (fx, fy) lies outside [0, W) x [0, H), bits 2..5 are clear and NO cell is read;
+ *   forward     c is empty, goal, floor, lava or an open door -- and allow_agent_overlap holds, or no agent row of the env has the
+ *               position (fx, fy): terminated agents count here (multigrid/base.py:425-429);
+ *   pickup      the agent carries nothing and c is a key, ball or box;
+ *   drop        the agent carries something, c is empty, and no agent row of the env has the position (fx, fy);
+ *   toggle      one of: c is a box; c is a door whose toggle changes it -- not locked, or locked while the agent carries a key of
+ *               the door's colour; in a MGX_KIND_REDBLUEDOORS env with the stale flag aux[4] set, (fx, fy) is the blue door
+ *               (aux[0], aux[1]) -- that door's OBJECT is closed whatever the grid shows, which `forward` sees too; in a
+ *               MGX_KIND_RULES env, some declared MGX_RULE_TOGGLES_AT rule k < aux[0] names (fx, fy), whatever its condition
+ *               (deliberately conservative: such a rule can end an episode by a toggle at a cell that holds nothing toggleable).
+ * This is `go && (nrow != row || writes)` of the step kernels' evaluation of one agent's action (csrc/mgx_rules.h: eval_agent) for
+ * the actions 0..5, plus the RULES clause; csrc/mgx_action_mask.h states it for both compilers.  Two guarantees:
+ *   SOUND   a clear bit means: the step in which this agent takes that action and every other agent takes `done` equals the step in
+ *           which it takes `done` too -- in state, aux, rewards and terminated flags.  It holds for the states reached by stepping
+ *           from generated, pool or reference states;
+ *   TIGHT   for every env kind but MGX_KIND_RULES: a set bit means that step differs from the all-`done` step in the grid or the
+ *           agent rows.
+ * A mask does not depend on the cell format (of a byte-grid value it sees type & 15, colour & 7, state & 3: the masks of STATE KEYS),
+ * nor on what a box holds.  It never reads or writes engine state: the layout marker, the episode counter, the generator's words,
+ * the running episode, np_random, the step count.
+ *
+ * mgx_action_mask: mask[i, a] = the mask of agent a of row src_idx[i] of the state set `src` (a NULL src_idx is the identity i;
+ * indices may repeat), i < n: u8[n, A].  With MGX_MASK_EXPAND the output is u8[n, A, 7] of 0 / 1, byte k = bit k (a `bool` tensor's
+ * bytes: `logits.masked_fill(~mask, -inf)`).  `mask` may have any alignment.  An index outside [0, rows) leaves its A (or 7 A)
+ * output bytes untouched and is counted as mgx_state_key counts it: bad[0] += 1, bad[1] = min(bad[1], i); `bad` may be NULL.  Of
+ * `src` only cells and agents (required) and aux (nullable: no stale door, no rules) are read.
+ * Return codes, in mgx_state_key's order: a bad spec (as mgx_env_copy), n < 0, NULL `src`, rows < 0, an unknown flag:
+ * MGX_ERR_INVALID_ARGUMENT; then n == 0: MGX_OK, nothing is launched; then NULL cells, agents or `mask`, or a misaligned pointer --
+ * 16 bytes for aux, 8 for agents and the index array, 4 for `bad`, 2 for 16-bit cells -- MGX_ERR_INVALID_ARGUMENT; more than INT_MAX
+ * workgroups, or more than 2^17 cells per env: MGX_ERR_UNSUPPORTED. */
+enum { MGX_MASK_EXPAND = 1 };
+
+int mgx_action_mask(const MgxSpec *spec, int64_t n, const MgxEnvRows *src, const int64_t *src_idx, uint32_t flags, uint8_t *mask,
+                    int32_t *bad, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -148,6 +148,21 @@ class EnvSnapshot:
         env.backend.state_key(n, members, self.rows, rows, flags, salt, keys, env._bad_words())
         return keys
 
+    def action_mask(self, rows: torch.Tensor | None = None, *, expand: bool = False, out: torch.Tensor | None = None) -> torch.Tensor:
+        """The effective-action masks of the snapshot rows `rows` (contiguous int64 [n] on the snapshot's device; None = every row, in
+        order) -- the launch of `BatchedMultiGridEnv.action_mask()` over the snapshot's own tensors, through the backend of the env
+        that took it: a row's masks are the masks that env had when the snapshot was taken.  A row outside [0, rows) leaves its masks
+        as they were and is reported by that env's `check_errors()`."""
+        env = self._env() if self._env is not None else None
+        if env is None:
+            raise RuntimeError("action_mask: the env this snapshot was taken from is gone (its backend makes the launch)")
+        env.join()
+        n = self.rows if rows is None else int(env._index_arg("action_mask", "rows", rows).shape[0])
+        mask = _mask_out("action_mask", out, n, self.spec.num_agents, expand, self.device)
+        members = {m: self.tensors.get(m) for m in ("cells", "agents", "aux")}
+        env.backend.action_mask(n, members, self.rows, rows, _lib.MASK_EXPAND if expand else 0, mask, env._bad_words())
+        return mask
+
 
 def _key_args(what: str, salt, step_count, rng) -> tuple:
     """(flags, salt) of mgx_state_key / mgx_obs_key"""
@@ -162,6 +177,15 @@ def _key_out(what: str, out, shape: tuple, device) -> torch.Tensor:
     if not torch.is_tensor(out) or out.dtype is not torch.int64 or tuple(out.shape) != tuple(shape) or out.device != device \
             or not out.is_contiguous():
         raise ValueError(f"{what}: out= must be a contiguous int64 tensor of shape {tuple(shape)} on {device}")
+    return out
+
+
+def _mask_out(what: str, out, n: int, A: int, expand: bool, device) -> torch.Tensor:
+    shape, dtype = ((n, A, 7), torch.bool) if expand else ((n, A), torch.uint8)
+    if out is None:
+        return torch.zeros(shape, dtype=dtype, device=device)
+    if not torch.is_tensor(out) or out.dtype is not dtype or tuple(out.shape) != shape or out.device != device or not out.is_contiguous():
+        raise ValueError(f"{what}: out= must be a contiguous {str(dtype).split('.')[-1]} tensor of shape {shape} on {device}")
     return out
 
 
@@ -1322,7 +1346,8 @@ class BatchedMultiGridEnv:
         self.join()
 
     def _bad_words(self) -> torch.Tensor:
-        """i32[2] on the device: how many pairs / keys the copy and key kernels skipped for an index out of range, and the first"""
+        """i32[2] on the device: how many pairs / keys / masks the copy, key and mask kernels skipped for an index out of range, and the
+        first"""
         if self._copy_bad is None:
             self._copy_bad = torch.tensor([0, INT32_MAX], dtype=torch.int32).to(self.device)
         return self._copy_bad
@@ -1484,6 +1509,30 @@ class BatchedMultiGridEnv:
         self.join()
         self.backend.obs_key(int(dir.numel()), obs, dir, salt, keys)
         return keys
+
+    # ------------------------------------------------------------------------------------------ action masks
+    def action_mask(self, env_ids: torch.Tensor | None = None, *, expand: bool = False, out: torch.Tensor | None = None) -> torch.Tensor:
+        """Which actions of every agent of the envs `env_ids` can do anything in the state they are in (include/mgx.h "ACTION
+        MASKS"): uint8 [n, A] on the device, bit k = `Action` k (left 0 .. toggle 5; `done` and bit 7 are never set), made by ONE
+        launch (mgx_action_mask) on the current stream -- no host round trip, no synchronisation, capturable in a graph.  With
+        `expand=True` the result is bool [n, A, 7], what `logits.masked_fill(~mask, -inf)` takes.
+
+        A clear bit is a promise: a step in which that agent takes that action and the others `done` equals the step in which it
+        takes `done` too -- a search need not fork that child.  A set bit means the step changes the grid or the agent rows (in an
+        env with declared hook rules: or may end the episode).  A terminated agent has no bit set; the turns are set for every other
+        agent.  The mask does not depend on the cell format and never on engine state.
+
+        env_ids  a contiguous int64 [n] tensor on the env's device (None = every env, in order), read by the kernel as it is; ids
+                 may repeat.  An id outside [0, batch) leaves its masks as they were and is reported by `check_errors()`.
+        out      a uint8 [n, A] (expand: bool [n, A, 7]) tensor on the env's device to write: a caller that masks every step
+                 allocates nothing."""
+        self._copy_entry("action_mask")
+        n = self.batch if env_ids is None else int(self._index_arg("action_mask", "env_ids", env_ids).shape[0])
+        mask = _mask_out("action_mask", out, n, self.spec.num_agents, expand, self._cells.device)
+        # (`_cells`, not `cells`: reading the grid keeps the layout marker's promises)
+        rows = {"cells": self._cells, "agents": self.agents, "aux": self.aux}
+        self.backend.action_mask(n, rows, self.batch, env_ids, _lib.MASK_EXPAND if expand else 0, mask, self._copy_bad)
+        return mask
 
     def outputs_to_host(self) -> dict:
         """Everything the last step / gen_obs handed back, on the host after ONE device-to-host copy (into a pinned buffer) and one

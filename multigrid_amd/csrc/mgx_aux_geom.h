@@ -138,6 +138,26 @@ inline int obs_key_group(int view_bytes) {
     return g;
 }
 
+// action_mask (mgx_action_mask.hip): every env a GROUP of lanes, the smallest power of two that holds its A agents (one lane per
+// agent; the lanes A .. group - 1 of a group idle), a wavefront `per` = 64 / group consecutive envs.  Wavefront w takes the envs
+// [w * per, min((w + 1) * per, n)): none is left without an env.
+constexpr int kMaskWpb = 4;                      // wavefronts per workgroup
+
+struct ActionMaskGeom {
+    int group, per;         // lanes per env (a power of two, A <= group <= 32); envs per wavefront
+    int64_t nwaves, blocks;
+};
+
+inline ActionMaskGeom action_mask_geom(int num_agents, int64_t n) {
+    ActionMaskGeom g;
+    g.group = 1;
+    while (g.group < num_agents && g.group < 64) g.group <<= 1;
+    g.per = 64 / g.group;
+    g.nwaves = (n + g.per - 1) / g.per;
+    g.blocks = (g.nwaves + kMaskWpb - 1) / kMaskWpb;
+    return g;
+}
+
 // persistent stepping: granules (4 action bytes each) per env and in all, and the reciprocal the producer kernels find a granule's
 // env with -- g / gpe by recip32, so the batch ends where that stops being exact (recip32_exact_below: 2^30 granules at gpe = 5,
 // 1 431 655 766 at gpe = 7, beyond 2^31 at every other gpe <= 8) or at 2^31 granules, whichever comes first

@@ -561,5 +561,16 @@ class HipBackend:
             rc = _lib.lib().mgx_obs_key(C.byref(self.sc), n, obs.data_ptr(), dir.data_ptr(), salt, keys.data_ptr(), _stream(dev))
         _lib.check(rc, "mgx_obs_key")
 
+    # ------------------------------------------------------------------------------------------ action masks
+    def action_mask(self, n, rows, n_rows, idx, flags, mask, bad):
+        """mgx_action_mask on torch's current stream: mask[i] (u8[n,A], or u8[n,A,7] of 0 / 1 with _lib.MASK_EXPAND in `flags`) = the
+        effective-action masks of row idx[i] of the state set `rows` (a dict of tensors holding `n_rows` rows: cells, agents, aux;
+        idx: i64[n] on the device, None = the identity, read by the kernel as it is).  `bad` i32[2] or None."""
+        s = self._env_rows(rows, n_rows)
+        dev = mask.device
+        with torch.cuda.device(dev):
+            rc = _lib.lib().mgx_action_mask(C.byref(self.sc), n, C.byref(s), _ptr(idx), flags, mask.data_ptr(), _ptr(bad), _stream(dev))
+        _lib.check(rc, "mgx_action_mask")
+
     def launch_info(self, B) -> dict:
         return _lib.launch_info(self.spec, B)
