@@ -888,6 +888,61 @@ enum { MGX_MASK_EXPAND = 1 };
 int mgx_action_mask(const MgxSpec *spec, int64_t n, const MgxEnvRows *src, const int64_t *src_idx, uint32_t flags, uint8_t *mask,
                     int32_t *bad, void *stream);
 
+/* DISTANCE FIELDS (additive to ABI 11): how many moves it takes, walls respected, from every cell of a grid -- and from every agent --
+ * to the nearest of a set of source cells, for chosen rows of a state set, made on the device in ONE launch: the heuristic of a
+ * best-first search over forked envs, the potential of a shaped reward, "is this layout solvable at all".  Build-defined: the
+ * reference has no such notion.
+ *
+ * CELL VALUES.  A cell is seen as `BatchedMultiGridEnv.grid` shows it: type & 15, colour & 7, state & 3 (the masks of STATE KEYS).  A
+ * box's content is never looked at.  The field does not depend on the cell format.
+ *
+ * PASSABLE.  A cell is passable when its type is empty (1), floor (3), goal (8) or lava (9), or a door (4) with state open (0):
+ * exactly the cells `forward` of ACTION MASKS enters when nobody stands there.  Type 0 and every other type are impassable.  Agents
+ * never block: the field is static geometry.  A stale RedBlueDoors door counts as the grid shows it (aux is not read).  The flags
+ * widen or narrow the set:
+ *   MGX_DIST_THROUGH_CLOSED   doors with state closed (1) are passable
+ *   MGX_DIST_THROUGH_LOCKED   doors with state locked (2) are passable      (a door with state 3 never is)
+ *   MGX_DIST_THROUGH_OBJECTS  key (5), ball (6) and box (7) cells are passable
+ *   MGX_DIST_AVOID_LAVA       lava is impassable
+ *
+ * SOURCES.  The members of the query MgxDistance; a cell is a source when any of them names it:
+ *   type_mask, colour_mask   bit t of type_mask: every cell of type t (0..15) whose colour c has bit c of colour_mask set; 0xFF = any
+ *                            colour.  colour_mask plays no part in the other selectors;
+ *   agent_mask               bit a: the position of agent row a < A, terminated or not, if it lies inside the grid (bits >= A: ignored);
+ *   points, num_points       i16[n, num_points, 2] of (x, y), per OUTPUT row i (not per source row).  A point outside the grid is
+ *                            ignored.  NULL with num_points 0: none;
+ *   flags                    the MGX_DIST_* above.
+ * A source need not be passable: the distance to a key is the distance to the key's own cell.
+ *
+ * THE FIELD.  Level 0 = the sources.  Level k + 1 = the 4-neighbours (x +- 1, y) and (x, y +- 1) of the cells of level k that are
+ * passable and in no earlier level.  d(p) = the level of p, and -1 for a cell in no level: walls, unreachable cells, every cell of an
+ * env without sources.  Distances count MOVES, not actions: turns are free (an agent that has to turn first needs more actions than
+ * d says).  Every distance is < H * W <= 4096.
+ *
+ * mgx_distance: for row src_idx[i] of the state set `src` (a NULL src_idx is the identity i; indices may repeat), i < n,
+ *   field       i16[n, H, W]   d of every cell                                                              nullable
+ *   agent_dist  i16[n, A]      d at agent row a's position, -1 if that lies outside the grid; a terminated agent is answered like
+ *                              any other                                                                    nullable
+ * At least one of the two must be given.  An index outside [0, rows) leaves its rows of both outputs untouched and is counted as
+ * mgx_action_mask counts it: bad[0] += 1, bad[1] = min(bad[1], i); `bad` may be NULL.  Of `src` only cells and agents are read.  The
+ * entry point never reads or writes engine state, aux, np_random or the step count.
+ * Return codes, in mgx_action_mask's order: a bad spec (as mgx_env_copy), n < 0, NULL `src`, rows < 0, NULL `q`, an unknown flag,
+ * num_points < 0: MGX_ERR_INVALID_ARGUMENT; then n == 0: MGX_OK, nothing is launched; then NULL cells or agents, both outputs NULL,
+ * NULL points with num_points > 0, or a misaligned pointer -- 2 bytes for field, agent_dist, points and 16-bit cells, 8 for agents
+ * and the index array, 4 for `bad` -- MGX_ERR_INVALID_ARGUMENT; then H > 64 or W > 64, or more than INT_MAX workgroups:
+ * MGX_ERR_UNSUPPORTED.  The side limit is the kernel's: one lane holds one grid row as a 64-bit mask, one wavefront's 64 lanes the
+ * rows of an env.  Every BASELINE configuration (up to 64 x 64) is inside it. */
+enum { MGX_DIST_THROUGH_CLOSED = 1, MGX_DIST_THROUGH_LOCKED = 2, MGX_DIST_THROUGH_OBJECTS = 4, MGX_DIST_AVOID_LAVA = 8 };
+
+typedef struct MgxDistance {
+    uint32_t type_mask, colour_mask, agent_mask, flags;
+    const int16_t *points;
+    int32_t num_points;
+} MgxDistance;
+
+int mgx_distance(const MgxSpec *spec, int64_t n, const MgxEnvRows *src, const int64_t *src_idx, const MgxDistance *q, int16_t *field,
+                 int16_t *agent_dist, int32_t *bad, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,7 +29,8 @@ EXPORTS = ("mgx_abi_version", "mgx_error_string", "mgx_last_hip_error", "mgx_gen
            "mgx_pack_grid_env", "mgx_check_grid", "mgx_pack_grid8_env", "mgx_unpack_grid8", "mgx_shape_key", "mgx_shape_register", "mgx_stage_generate",
            "mgx_persistent_waves", "mgx_step_persistent", "mgx_persistent_post", "mgx_persistent_wait", "mgx_persistent_feed",
            "mgx_rollout_info", "mgx_render_atlas", "mgx_render", "mgx_reset_select", "mgx_reset_generate_select",
-           "mgx_episode_stats", "mgx_episode_restart", "mgx_env_copy", "mgx_state_key", "mgx_obs_key", "mgx_action_mask")
+           "mgx_episode_stats", "mgx_episode_restart", "mgx_env_copy", "mgx_state_key", "mgx_obs_key", "mgx_action_mask",
+           "mgx_distance")
 
 
 class MgxLaunchInfo(C.Structure):
@@ -110,6 +111,14 @@ class MgxEnvRows(C.Structure):
 STAGE_NONE, STAGE_CANDIDATES, STAGE_SNAPSHOTS = 0, 1, 2      # mgx_env_copy's stage_mode
 KEY_STEP_COUNT, KEY_RNG = 1, 2                               # mgx_state_key's flags (MGX_KEY_*)
 MASK_EXPAND = 1                                              # mgx_action_mask's flag (MGX_MASK_EXPAND)
+DIST_THROUGH_CLOSED, DIST_THROUGH_LOCKED, DIST_THROUGH_OBJECTS, DIST_AVOID_LAVA = 1, 2, 4, 8     # mgx_distance's flags (MGX_DIST_*)
+DIST_MAX_SIDE = 64                                           # mgx_distance: one lane per grid row, one bit per column
+
+
+class MgxDistanceC(C.Structure):
+    """include/mgx.h: struct MgxDistance (the sources and flags of a distance query)."""
+    _fields_ = [("type_mask", C.c_uint32), ("colour_mask", C.c_uint32), ("agent_mask", C.c_uint32), ("flags", C.c_uint32),
+                ("points", C.c_void_p), ("num_points", C.c_int32)]
 
 GEN_KINDS = {"empty_fixed": 0, "empty_random": 1, "blockedunlockpickup": 2, "redbluedoors": 3, "lockedhallway": 4, "playground": 5}
 
@@ -228,6 +237,10 @@ def lib() -> C.CDLL:
     if is_product_lib() or hasattr(L, "mgx_action_mask"):
         L.mgx_action_mask.restype = C.c_int
         L.mgx_action_mask.argtypes = [C.POINTER(MgxSpecC), i64, C.POINTER(MgxEnvRows), vp, C.c_uint32, vp, vp, vp]
+    # (... or the distance fields: only distance_field() / agent_distance() need them)
+    if is_product_lib() or hasattr(L, "mgx_distance"):
+        L.mgx_distance.restype = C.c_int
+        L.mgx_distance.argtypes = [C.POINTER(MgxSpecC), i64, C.POINTER(MgxEnvRows), vp, C.POINTER(MgxDistanceC), vp, vp, vp, vp]
     if L.mgx_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH}: ABI version {L.mgx_abi_version()} != {ABI_VERSION}; rebuild it")
     _lib = L

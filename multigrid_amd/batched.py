@@ -163,6 +163,33 @@ class EnvSnapshot:
         env.backend.action_mask(n, members, self.rows, rows, _lib.MASK_EXPAND if expand else 0, mask, env._bad_words())
         return mask
 
+    def _distance(self, what: str, rows, query: dict, out, field: bool) -> torch.Tensor:
+        env = self._env() if self._env is not None else None
+        if env is None:
+            raise RuntimeError(f"{what}: the env this snapshot was taken from is gone (its backend makes the launch)")
+        env.join()
+        n = self.rows if rows is None else int(env._index_arg(what, "rows", rows).shape[0])
+        q = _dist_query(what, self.spec, n, self.device, **query)
+        res = _dist_out(what, out, n, self.spec, field, self.device)
+        members = {m: self.tensors.get(m) for m in ("cells", "agents")}
+        env.backend.distance(n, members, self.rows, rows, q, res if field else None, None if field else res, env._bad_words())
+        return res
+
+    def distance_field(self, rows: torch.Tensor | None = None, *, types=None, colors=None, agents=None, points=None, through=(),
+                       avoid_lava: bool = False, out: torch.Tensor | None = None) -> torch.Tensor:
+        """The walking-distance fields of the snapshot rows `rows` (contiguous int64 [n] on the snapshot's device; None = every row,
+        in order) -- the launch of `BatchedMultiGridEnv.distance_field()` over the snapshot's own tensors, through the backend of the
+        env that took it.  A row outside [0, rows) leaves its field as it was and is reported by that env's `check_errors()`."""
+        query = dict(types=types, colors=colors, agents=agents, points=points, through=through, avoid_lava=avoid_lava)
+        return self._distance("distance_field", rows, query, out, True)
+
+    def agent_distance(self, rows: torch.Tensor | None = None, *, types=None, colors=None, agents=None, points=None, through=(),
+                       avoid_lava: bool = False, out: torch.Tensor | None = None) -> torch.Tensor:
+        """The agents' walking distances in the snapshot rows `rows`: `BatchedMultiGridEnv.agent_distance()` over the snapshot's
+        own tensors (see `distance_field()` above)."""
+        query = dict(types=types, colors=colors, agents=agents, points=points, through=through, avoid_lava=avoid_lava)
+        return self._distance("agent_distance", rows, query, out, False)
+
 
 def _key_args(what: str, salt, step_count, rng) -> tuple:
     """(flags, salt) of mgx_state_key / mgx_obs_key"""
@@ -186,6 +213,61 @@ def _mask_out(what: str, out, n: int, A: int, expand: bool, device) -> torch.Ten
         return torch.zeros(shape, dtype=dtype, device=device)
     if not torch.is_tensor(out) or out.dtype is not dtype or tuple(out.shape) != shape or out.device != device or not out.is_contiguous():
         raise ValueError(f"{what}: out= must be a contiguous {str(dtype).split('.')[-1]} tensor of shape {shape} on {device}")
+    return out
+
+
+_DIST_THROUGH = {"closed": _lib.DIST_THROUGH_CLOSED, "locked": _lib.DIST_THROUGH_LOCKED, "objects": _lib.DIST_THROUGH_OBJECTS}
+
+
+def _dist_bits(what: str, name: str, values, below: int, why: str) -> int:
+    """the bit mask of an iterable of small ints (enum members included)"""
+    if isinstance(values, (str, bytes)) or torch.is_tensor(values):
+        raise ValueError(f"{what}: {name} must be an iterable of ints")
+    mask = 0
+    try:
+        items = list(values)
+    except TypeError:
+        raise ValueError(f"{what}: {name} must be an iterable of ints") from None
+    for v in items:
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < below:
+            raise ValueError(f"{what}: {name} holds {v!r}: {why}")
+        mask |= 1 << int(v)
+    return mask
+
+
+def _dist_query(what: str, spec, n: int, device, types=None, colors=None, agents=None, points=None, through=(), avoid_lava=False) -> dict:
+    """The query of mgx_distance (include/mgx.h "DISTANCE FIELDS": MgxDistance) from the keyword arguments of distance_field() /
+    agent_distance(): {type_mask, colour_mask, agent_mask, flags, points}."""
+    A = spec.num_agents
+    type_mask = 0 if types is None else _dist_bits(what, "types", types, 16, "a Type or an int in [0, 16)")
+    colour_mask = 0xFF if colors is None else _dist_bits(what, "colors", colors, 8, "a Color or an int in [0, 8)")
+    agent_mask = 0 if agents is None else _dist_bits(what, "agents", agents, A, f"an agent index must lie in [0, {A})")
+    if colors is not None and types is None:
+        raise ValueError(f"{what}: colors= narrows the cells that types= selects: pass types= with it")
+    if isinstance(through, str):
+        through = (through,)
+    flags = _lib.DIST_AVOID_LAVA if avoid_lava else 0
+    for w in through:
+        if w not in _DIST_THROUGH:
+            raise ValueError(f"{what}: through= holds {w!r}: it must be a subset of {sorted(_DIST_THROUGH)}")
+        flags |= _DIST_THROUGH[w]
+    if points is not None:
+        if not torch.is_tensor(points) or points.dtype is not torch.int16 or points.dim() != 3 or int(points.shape[0]) != n \
+                or int(points.shape[2]) != 2 or points.device != device or not points.is_contiguous():
+            raise ValueError(f"{what}: points must be a contiguous int16 tensor of shape ({n}, P, 2) on {device}: (x, y) per output row")
+        if int(points.shape[1]) == 0:
+            points = None
+    if not type_mask and not agent_mask and points is None:
+        raise ValueError(f"{what}: the query names no source: pass types=, agents= or points=")
+    return {"type_mask": type_mask, "colour_mask": colour_mask, "agent_mask": agent_mask, "flags": flags, "points": points}
+
+
+def _dist_out(what: str, out, n: int, spec, field: bool, device) -> torch.Tensor:
+    shape = (n, spec.height, spec.width) if field else (n, spec.num_agents)
+    if out is None:
+        return torch.full(shape, -1, dtype=torch.int16, device=device)
+    if not torch.is_tensor(out) or out.dtype is not torch.int16 or tuple(out.shape) != shape or out.device != device or not out.is_contiguous():
+        raise ValueError(f"{what}: out= must be a contiguous int16 tensor of shape {shape} on {device}")
     return out
 
 
@@ -1533,6 +1615,48 @@ class BatchedMultiGridEnv:
         rows = {"cells": self._cells, "agents": self.agents, "aux": self.aux}
         self.backend.action_mask(n, rows, self.batch, env_ids, _lib.MASK_EXPAND if expand else 0, mask, self._copy_bad)
         return mask
+
+    # ------------------------------------------------------------------------------------------ distance fields
+    def _distance(self, what: str, env_ids, query: dict, out, field: bool) -> torch.Tensor:
+        self._copy_entry(what)
+        n = self.batch if env_ids is None else int(self._index_arg(what, "env_ids", env_ids).shape[0])
+        dev = self._cells.device
+        q = _dist_query(what, self.spec, n, dev, **query)
+        res = _dist_out(what, out, n, self.spec, field, dev)
+        # (`_cells`, not `cells`: reading the grid keeps the layout marker's promises)
+        rows = {"cells": self._cells, "agents": self.agents}
+        self.backend.distance(n, rows, self.batch, env_ids, q, res if field else None, None if field else res, self._copy_bad)
+        return res
+
+    def distance_field(self, env_ids: torch.Tensor | None = None, *, types=None, colors=None, agents=None, points=None, through=(),
+                       avoid_lava: bool = False, out: torch.Tensor | None = None) -> torch.Tensor:
+        """How many moves every cell of the envs `env_ids` lies from the nearest source cell, walls respected (include/mgx.h
+        "DISTANCE FIELDS"): int16 [n, H, W] on the device, -1 for walls, unreachable cells and envs without a source, made by ONE
+        launch (mgx_distance) on the current stream -- no host round trip, no synchronisation, capturable in a graph.  Distances
+        count moves, not actions: turns are free.  Agents never block; a walk enters what `forward` enters when nobody stands there
+        (empty, floor, goal, lava, open doors).  A source need not be passable: the distance to a key is that to the key's cell.
+
+        types       Type members or ints: every cell of such a type is a source ...
+        colors      ... if it has one of these Color members or ints (None = any colour; needs types=)
+        agents      agent indices: the positions of these agents (terminated or not) are sources
+        points      a contiguous int16 [n, P, 2] tensor on the env's device: (x, y) sources per output row; points outside the
+                    grid are ignored
+        through     a subset of {"closed", "locked", "objects"}: closed doors, locked doors, key / ball / box cells are passable
+        avoid_lava  lava is impassable
+        env_ids     a contiguous int64 [n] tensor on the env's device (None = every env, in order), read by the kernel as it is;
+                    ids may repeat.  An id outside [0, batch) leaves its rows as they were and is reported by `check_errors()`.
+        out         an int16 [n, H, W] tensor on the env's device to write: a caller that asks every step allocates nothing.
+        Sides above 64 are refused (the kernel holds a grid row in one 64-bit word, an env's rows in one wavefront)."""
+        query = dict(types=types, colors=colors, agents=agents, points=points, through=through, avoid_lava=avoid_lava)
+        return self._distance("distance_field", env_ids, query, out, True)
+
+    def agent_distance(self, env_ids: torch.Tensor | None = None, *, types=None, colors=None, agents=None, points=None, through=(),
+                       avoid_lava: bool = False, out: torch.Tensor | None = None) -> torch.Tensor:
+        """The distance field of `distance_field()` -- same arguments, same launch -- read at the agents' positions only: int16
+        [n, A], the number of moves from agent a to the nearest source, -1 when there is no way (or the agent row lies outside the
+        grid).  A terminated agent is answered like any other.  `out`: an int16 [n, A] tensor to write."""
+        query = dict(types=types, colors=colors, agents=agents, points=points, through=through, avoid_lava=avoid_lava)
+        return self._distance("agent_distance", env_ids, query, out, False)
 
     def outputs_to_host(self) -> dict:
         """Everything the last step / gen_obs handed back, on the host after ONE device-to-host copy (into a pinned buffer) and one

@@ -158,6 +158,31 @@ inline ActionMaskGeom action_mask_geom(int num_agents, int64_t n) {
     return g;
 }
 
+// distance (mgx_distance.hip): every env a GROUP of lanes, the smallest power of two that holds its H grid rows (one lane per row, at
+// least 4; the lanes H .. group - 1 of a group idle), a wavefront `per` = 64 / group consecutive envs.  Wavefront w takes the envs
+// [w * per, min((w + 1) * per, n)): none is left without an env.  The tile is loaded and the field stored in rounds of 64 lanes:
+// `wp` lanes per grid row (the smallest power of two that holds its W columns), `rpb` = 64 / wp rows per round.
+constexpr int kDistWpb = 4;                      // wavefronts per workgroup
+
+struct DistanceGeom {
+    int group, per;         // lanes per env (a power of two, max(H, 4) <= group <= 64); envs per wavefront
+    int wp, rpb;            // lanes per grid row of a load / store round; rows per round
+    int64_t nwaves, blocks;
+};
+
+inline DistanceGeom distance_geom(int W, int H, int64_t n) {
+    DistanceGeom g;
+    g.group = 4;
+    while (g.group < H && g.group < 64) g.group <<= 1;
+    g.per = 64 / g.group;
+    g.wp = 1;
+    while (g.wp < W && g.wp < 64) g.wp <<= 1;
+    g.rpb = 64 / g.wp;
+    g.nwaves = (n + g.per - 1) / g.per;
+    g.blocks = (g.nwaves + kDistWpb - 1) / kDistWpb;
+    return g;
+}
+
 // persistent stepping: granules (4 action bytes each) per env and in all, and the reciprocal the producer kernels find a granule's
 // env with -- g / gpe by recip32, so the batch ends where that stops being exact (recip32_exact_below: 2^30 granules at gpe = 5,
 // 1 431 655 766 at gpe = 7, beyond 2^31 at every other gpe <= 8) or at 2^31 granules, whichever comes first

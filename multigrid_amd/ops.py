@@ -572,5 +572,21 @@ class HipBackend:
             rc = _lib.lib().mgx_action_mask(C.byref(self.sc), n, C.byref(s), _ptr(idx), flags, mask.data_ptr(), _ptr(bad), _stream(dev))
         _lib.check(rc, "mgx_action_mask")
 
+    # ------------------------------------------------------------------------------------------ distance fields
+    def distance(self, n, rows, n_rows, idx, query, field, agent_dist, bad):
+        """mgx_distance on torch's current stream: the walking distances of row idx[i] of the state set `rows` (a dict of tensors
+        holding `n_rows` rows: cells, agents; idx: i64[n] on the device, None = the identity, read by the kernel as it is) to the
+        sources of `query` = {type_mask, colour_mask, agent_mask, flags, points (i16[n,P,2] or None)}, into field i16[n,H,W] and / or
+        agent_dist i16[n,A] (one of them may be None).  `bad` i32[2] or None."""
+        s = self._env_rows(rows, n_rows)
+        pts = query.get("points")
+        q = _lib.MgxDistanceC(query["type_mask"], query["colour_mask"], query["agent_mask"], query["flags"], _ptr(pts),
+                              0 if pts is None else int(pts.shape[1]))
+        dev = (field if field is not None else agent_dist).device
+        with torch.cuda.device(dev):
+            rc = _lib.lib().mgx_distance(C.byref(self.sc), n, C.byref(s), _ptr(idx), C.byref(q), _ptr(field), _ptr(agent_dist), _ptr(bad),
+                                         _stream(dev))
+        _lib.check(rc, "mgx_distance")
+
     def launch_info(self, B) -> dict:
         return _lib.launch_info(self.spec, B)
