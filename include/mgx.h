@@ -943,6 +943,79 @@ typedef struct MgxDistance {
 int mgx_distance(const MgxSpec *spec, int64_t n, const MgxEnvRows *src, const int64_t *src_idx, const MgxDistance *q, int16_t *field,
                  int16_t *agent_dist, int32_t *bad, void *stream);
 
+/* KEY TABLES (additive to ABI 11): the set of keys already seen, kept on the device -- a transposition table for a search over forked
+ * envs, the cell archive of Go-Explore, visit counts for count-based exploration.  A table maps a 64-bit key (mgx_state_key,
+ * mgx_obs_key, or any number of the caller's) to a stable ENTRY ID in [0, capacity): the caller keeps what it wants per entry (best
+ * score, snapshot row, parent) in arrays of its own indexed by that id.  A batch of keys is inserted in TWO launches and looked up in
+ * ONE, in constant memory, without host work or synchronisation, capturable in a graph.  Build-defined: the reference has no such notion.
+ *
+ * STORAGE.  A table is caller-owned device memory, described by MgxKeyTable:
+ *   capacity   a power of two, MGX_KEY_MIN_CAPACITY (64) <= capacity <= MGX_KEY_MAX_CAPACITY (2^30): the number of slots
+ *   keys       u64[capacity]   the key a slot holds; 0 = the slot is empty                                 8-byte aligned
+ *   tag        u64[capacity]   epoch << 32 | (0xFFFFFFFF - i): the last call that inserted the slot's key, and the smallest index i
+ *                              of that call that held it                                                   8-byte aligned
+ *   born       u32[capacity]   the epoch of the call that placed the key                                  4-byte aligned
+ *   visits     u32[capacity]   how often the key has been inserted (counting calls only)                   4-byte aligned
+ *   ctrl       u32[MGX_KEY_CTRL_WORDS = 8]  [0] the epoch of the insert whose first launch ran last, [1] the epoch of the last
+ *                              finished insert, [2] MGX_KEY_CTRL_ENTRIES: occupied slots, [3] MGX_KEY_CTRL_DROPPED: dropped indices
+ *                              since the caller last zeroed the word, [4..7] zero, reserved               4-byte aligned
+ * 24 * capacity + 32 bytes in all.  ALL-ZERO STORAGE IS THE EMPTY TABLE: a table is made, and cleared, by a zero fill (hipMemsetAsync
+ * is capturable); epochs start at 1 again.  An epoch is a call's number, 32 bits: after 2^32 - 1 inserts without a clear the epochs
+ * wrap and is_new / first are no longer right -- documented, not handled.  The caller may zero ctrl[3] at any time between calls.
+ * One table takes one call at a time: two calls on one table must be ordered by their streams.
+ *
+ * KEY 0 marks an empty slot, so the key 0 is stored and answered as the key 1: one more 2^-64 alias, like any collision of the keys.
+ *
+ * PLACEMENT.  Open addressing, linear probing.  With k the canonical key (0 -> 1), home(k) = splitmix64(k) & (capacity - 1)
+ * (splitmix64 of STATE KEYS: callers may pass keys that are not hash outputs).  A key is looked for, and placed, only in its WINDOW:
+ * the min(MGX_KEY_MAX_PROBE = 1024, capacity) slots home, home + 1, ... taken mod capacity (the window wraps at the table's end), in
+ * that order, at the first slot that holds the key or is empty.  Entries are never removed.  THE INVARIANT everything rests on: a
+ * slot goes from empty to one key exactly once and never changes again -- so every slot before a key's slot in its window is
+ * occupied by another key, and a lookup may stop at the first empty slot.
+ *
+ * mgx_key_insert(table, n, keys i64[n], flags, entry i64[n], is_new u8[n], first i64[n], visits i32[n], stream); `entry` is required,
+ * is_new, first and visits are nullable.  THE RULE: apart from the VALUES of `entry`, the outputs are those of inserting keys[0..n)
+ * one after another in index order.
+ *   entry[i]    the id of the key's entry = its slot, in [0, capacity): equal for equal keys, different for different keys, the same
+ *               in every later call until the table is cleared; -1 if the key could not be placed (FULL).  Which number an entry gets
+ *               depends on the order in which the device's threads arrive and is NOT reproducible from run to run.  All below is.
+ *   is_new[i]   1 iff the key was not in the table before this call and no j < i of this call holds the same key: exactly one index
+ *               per new key, the smallest; else 0
+ *   first[i]    the smallest j of this call with keys[j] == keys[i] (canonical keys)
+ *   visits[i]   how many times the key has been inserted in the table's life by counting calls, this call included: the count AFTER
+ *               the call, the same for every index of a key
+ * With the flag MGX_KEY_NO_COUNT the call counts nothing (pure set semantics); visits[i] is then the count as it stood.
+ * FULL: an index whose key's window holds neither the key nor an empty slot is DROPPED: entry = -1, is_new = 0, first = -1, visits = 0,
+ * and ctrl[MGX_KEY_CTRL_DROPPED] goes up by one per dropped index.  All indices of a call with one key share its fate (by the
+ * invariant: whoever placed the key left it where every other walk of that window meets it).  WHICH keys are dropped when more new
+ * keys arrive than their windows hold is arrival order, hence unspecified; a non-zero counter has told the caller.
+ * ctrl[MGX_KEY_CTRL_ENTRIES] counts the placed keys.
+ *
+ * mgx_key_lookup(table, n, keys i64[n], entry i64[n], visits i32[n] nullable, stream): read-only.  entry[i] = the key's entry id, -1
+ * for a key the table does not hold; visits[i] its count, 0 for an absent key.
+ *
+ * Return codes, in mgx_state_key's order: a NULL table, a capacity that is not a power of two in range, n < 0, an unknown flag:
+ * MGX_ERR_INVALID_ARGUMENT; then n == 0: MGX_OK, nothing is launched; then a NULL array of the table, NULL `keys` or `entry`, or a
+ * misaligned pointer -- 8 bytes for keys, entry, first and the table's 64-bit arrays, 4 for visits and the table's 32-bit arrays --
+ * MGX_ERR_INVALID_ARGUMENT; then n >= 2^31 (an index must fit the tag's low word with room to spare), or more than INT_MAX
+ * workgroups: MGX_ERR_UNSUPPORTED.  csrc/mgx_key_table.h states the rule for both compilers. */
+enum { MGX_KEY_NO_COUNT = 1 };
+enum { MGX_KEY_MAX_PROBE = 1024, MGX_KEY_MIN_CAPACITY = 64, MGX_KEY_MAX_CAPACITY = 1 << 30, MGX_KEY_CTRL_WORDS = 8,
+       MGX_KEY_CTRL_ENTRIES = 2, MGX_KEY_CTRL_DROPPED = 3 };
+
+typedef struct MgxKeyTable {
+    int64_t capacity;
+    uint64_t *keys;
+    uint64_t *tag;
+    uint32_t *born;
+    uint32_t *visits;
+    uint32_t *ctrl;
+} MgxKeyTable;
+
+int mgx_key_insert(const MgxKeyTable *table, int64_t n, const int64_t *keys, uint32_t flags, int64_t *entry, uint8_t *is_new,
+                   int64_t *first, int32_t *visits, void *stream);
+int mgx_key_lookup(const MgxKeyTable *table, int64_t n, const int64_t *keys, int64_t *entry, int32_t *visits, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

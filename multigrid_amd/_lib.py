@@ -30,7 +30,7 @@ EXPORTS = ("mgx_abi_version", "mgx_error_string", "mgx_last_hip_error", "mgx_gen
            "mgx_persistent_waves", "mgx_step_persistent", "mgx_persistent_post", "mgx_persistent_wait", "mgx_persistent_feed",
            "mgx_rollout_info", "mgx_render_atlas", "mgx_render", "mgx_reset_select", "mgx_reset_generate_select",
            "mgx_episode_stats", "mgx_episode_restart", "mgx_env_copy", "mgx_state_key", "mgx_obs_key", "mgx_action_mask",
-           "mgx_distance")
+           "mgx_distance", "mgx_key_insert", "mgx_key_lookup")
 
 
 class MgxLaunchInfo(C.Structure):
@@ -119,6 +119,16 @@ class MgxDistanceC(C.Structure):
     """include/mgx.h: struct MgxDistance (the sources and flags of a distance query)."""
     _fields_ = [("type_mask", C.c_uint32), ("colour_mask", C.c_uint32), ("agent_mask", C.c_uint32), ("flags", C.c_uint32),
                 ("points", C.c_void_p), ("num_points", C.c_int32)]
+
+
+class MgxKeyTableC(C.Structure):
+    """include/mgx.h: struct MgxKeyTable (a device key table: its capacity and its five arrays)."""
+    _fields_ = [("capacity", C.c_int64)] + [(n, C.c_void_p) for n in ("keys", "tag", "born", "visits", "ctrl")]
+
+
+KEY_NO_COUNT = 1                                             # mgx_key_insert's flag (MGX_KEY_NO_COUNT)
+KEY_MAX_PROBE, KEY_MIN_CAPACITY, KEY_MAX_CAPACITY, KEY_CTRL_WORDS = 1024, 64, 1 << 30, 8      # MGX_KEY_*
+KEY_CTRL_ENTRIES, KEY_CTRL_DROPPED = 2, 3                    # the control words a caller reads (MGX_KEY_CTRL_*)
 
 GEN_KINDS = {"empty_fixed": 0, "empty_random": 1, "blockedunlockpickup": 2, "redbluedoors": 3, "lockedhallway": 4, "playground": 5}
 
@@ -241,6 +251,12 @@ def lib() -> C.CDLL:
     if is_product_lib() or hasattr(L, "mgx_distance"):
         L.mgx_distance.restype = C.c_int
         L.mgx_distance.argtypes = [C.POINTER(MgxSpecC), i64, C.POINTER(MgxEnvRows), vp, C.POINTER(MgxDistanceC), vp, vp, vp, vp]
+    # (... or the key tables: only KeyTable needs them)
+    if is_product_lib() or hasattr(L, "mgx_key_insert"):
+        L.mgx_key_insert.restype = C.c_int
+        L.mgx_key_insert.argtypes = [C.POINTER(MgxKeyTableC), i64, vp, C.c_uint32, vp, vp, vp, vp, vp]
+        L.mgx_key_lookup.restype = C.c_int
+        L.mgx_key_lookup.argtypes = [C.POINTER(MgxKeyTableC), i64, vp, vp, vp, vp]
     if L.mgx_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH}: ABI version {L.mgx_abi_version()} != {ABI_VERSION}; rebuild it")
     _lib = L

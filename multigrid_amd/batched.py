@@ -1592,6 +1592,14 @@ class BatchedMultiGridEnv:
         self.backend.obs_key(int(dir.numel()), obs, dir, salt, keys)
         return keys
 
+    def key_table(self, capacity: int):
+        """A `multigrid_amd.KeyTable` of `capacity` slots (a power of two, 64 .. 2**30) on the env's device, launched through the
+        env's backend: the set of keys already seen -- `state_key()` / `obs_key()` outputs of this env, its snapshots or any other
+        int64 numbers -- with a stable entry id per key, visit counts and "which of these are new" (include/mgx.h "KEY TABLES").  The
+        table belongs to the caller, not to the env: nothing the env does reads or writes it."""
+        from .key_table import KeyTable
+        return KeyTable(capacity, self._cells.device, backend=self.backend)
+
     # ------------------------------------------------------------------------------------------ action masks
     def action_mask(self, env_ids: torch.Tensor | None = None, *, expand: bool = False, out: torch.Tensor | None = None) -> torch.Tensor:
         """Which actions of every agent of the envs `env_ids` can do anything in the state they are in (include/mgx.h "ACTION

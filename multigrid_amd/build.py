@@ -32,10 +32,11 @@ UNITS = ([("mgx_kernels", os.path.join(CSRC, "mgx_kernels.hip"), ()), ("mgx_aux"
           ("mgx_stats", os.path.join(CSRC, "mgx_stats.hip"), ()), ("mgx_env_copy", os.path.join(CSRC, "mgx_env_copy.hip"), ()),
           ("mgx_state_key", os.path.join(CSRC, "mgx_state_key.hip"), ()),
           ("mgx_action_mask", os.path.join(CSRC, "mgx_action_mask.hip"), ()),
-          ("mgx_distance", os.path.join(CSRC, "mgx_distance.hip"), ())]
+          ("mgx_distance", os.path.join(CSRC, "mgx_distance.hip"), ()),
+          ("mgx_key_table", os.path.join(CSRC, "mgx_key_table.hip"), ())]
          + [(f"mgx_fused_v{v}", os.path.join(CSRC, "mgx_fused_inst.hip"), (f"MGX_INST_V={v}",)) for v in VIEWS])
 SRCS = sorted({u[1] for u in UNITS})
-DEPS = SRCS + [os.path.join(CSRC, "mgx_action_mask.h"), os.path.join(CSRC, "mgx_aux_geom.h"), os.path.join(CSRC, "mgx_distance.h"), os.path.join(CSRC, "mgx_fused.h"), os.path.join(CSRC, "mgx_fused_body.inc"), os.path.join(CSRC, "mgx_host.h"), os.path.join(CSRC, "mgx_layout_gen.h"), os.path.join(CSRC, "mgx_rules.h"),
+DEPS = SRCS + [os.path.join(CSRC, "mgx_action_mask.h"), os.path.join(CSRC, "mgx_aux_geom.h"), os.path.join(CSRC, "mgx_distance.h"), os.path.join(CSRC, "mgx_fused.h"), os.path.join(CSRC, "mgx_fused_body.inc"), os.path.join(CSRC, "mgx_host.h"), os.path.join(CSRC, "mgx_key_table.h"), os.path.join(CSRC, "mgx_layout_gen.h"), os.path.join(CSRC, "mgx_rules.h"),
                os.path.join(CSRC, "mgx_render.h"), os.path.join(CSRC, "mgx_state_key.h"), os.path.join(ROOT, "include", "mgx.h")]
 LIB = os.path.join(HERE, "lib", "libmgx.so")
 LIB_DBG = os.path.join(HERE, "lib", "libmgx_dbg.so")

@@ -119,7 +119,48 @@ def _load_compiled_ops():
 _load_compiled_ops()
 
 
-class HipBackend:
+class KeyTableOps:
+    """The launchers of the device key tables (include/mgx.h "KEY TABLES").  They need no env spec: `multigrid_amd.KeyTable` makes
+    one of these for a table that belongs to no env; HipBackend inherits them for `BatchedMultiGridEnv.key_table()`."""
+
+    name = "hip"
+
+    def __init__(self, device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError(
+                f"multigrid_amd runs on MI355X only: device must be a HIP ('cuda') device, got '{device}'. "
+                "There is no CPU fallback.")
+        if not torch.cuda.is_available():
+            raise RuntimeError("multigrid_amd: no HIP device is visible (torch.cuda.is_available() is False)")
+        _lib.lib()  # raises ImportError if the extension is missing
+        self.device = device
+
+    @staticmethod
+    def _key_table(table: dict):
+        """table = {capacity, keys, tag, born, visits, ctrl} of include/mgx.h MgxKeyTable (KeyTable.storage)"""
+        return _lib.MgxKeyTableC(table["capacity"], *[table[m].data_ptr() for m in ("keys", "tag", "born", "visits", "ctrl")])
+
+    def key_insert(self, table, n, keys, flags, entry, is_new, first, visits):
+        """mgx_key_insert on torch's current stream (two launches): keys i64[n] into the table `table` (a dict of its capacity and
+        its tensors); entry i64[n], and is_new u8 / bool [n], first i64[n], visits i32[n] or None.  `flags`: _lib.KEY_NO_COUNT."""
+        t = self._key_table(table)
+        dev = keys.device
+        with torch.cuda.device(dev):
+            rc = _lib.lib().mgx_key_insert(C.byref(t), n, keys.data_ptr(), flags, entry.data_ptr(), _ptr(is_new), _ptr(first),
+                                           _ptr(visits), _stream(dev))
+        _lib.check(rc, "mgx_key_insert")
+
+    def key_lookup(self, table, n, keys, entry, visits):
+        """mgx_key_lookup on torch's current stream (one launch, read-only): entry i64[n] (-1 = absent), visits i32[n] or None."""
+        t = self._key_table(table)
+        dev = keys.device
+        with torch.cuda.device(dev):
+            rc = _lib.lib().mgx_key_lookup(C.byref(t), n, keys.data_ptr(), entry.data_ptr(), _ptr(visits), _stream(dev))
+        _lib.check(rc, "mgx_key_lookup")
+
+
+class HipBackend(KeyTableOps):
     """Pre-bound launcher: the state and output tensors of one BatchedMultiGridEnv, validated once."""
 
     name = "hip"
