@@ -18,8 +18,9 @@ import weakref
 import numpy as np
 import torch
 
-from . import _lib, layouts, rng as rnglib
+from . import _lib, layouts, rng as rnglib, row_queries
 from .constants import NO_ACTION, Action, Type
+from .row_queries import RowSet, _key_args, _out
 from .spec import EnvSpec
 
 INT32_MAX = 2 ** 31 - 1
@@ -131,49 +132,28 @@ class EnvSnapshot:
     def nbytes(self) -> int:
         return sum(t.numel() * t.element_size() for t in self.tensors.values())
 
+    def _row_set(self, what: str) -> RowSet:
+        """This snapshot's own tensors as the rows of a query (row_queries.py), launched by the env that took it."""
+        env = self._env() if self._env is not None else None
+        if env is None:
+            raise RuntimeError(f"{what}: the env this snapshot was taken from is gone (its backend makes the launch)")
+        env.join()
+        return RowSet(what, env, self.tensors, self.rows, self.device, "rows")
+
     def state_key(self, rows: torch.Tensor | None = None, *, salt: int = 0, step_count: bool = False, rng: bool = False,
                   out: torch.Tensor | None = None) -> torch.Tensor:
         """The keys of the snapshot rows `rows` (contiguous int64 [n] on the snapshot's device; None = every row, in order) -- the
         launch of `BatchedMultiGridEnv.state_key()` over the snapshot's own tensors, through the backend of the env that took it: a
         row's key is the key that env had when the snapshot was taken.  A row outside [0, rows) leaves its key as it was and is
         reported by that env's `check_errors()`."""
-        env = self._env() if self._env is not None else None
-        if env is None:
-            raise RuntimeError("state_key: the env this snapshot was taken from is gone (its backend makes the launch)")
-        env.join()
-        n = self.rows if rows is None else int(env._index_arg("state_key", "rows", rows).shape[0])
-        flags, salt = _key_args("state_key", salt, step_count, rng)
-        keys = _key_out("state_key", out, (n,), self.device)
-        members = {m: self.tensors.get(m) for m in ("cells", "agents", "rng", "step_count", "aux")}
-        env.backend.state_key(n, members, self.rows, rows, flags, salt, keys, env._bad_words())
-        return keys
+        return row_queries.state_key(self._row_set("state_key"), rows, salt, step_count, rng, out)
 
     def action_mask(self, rows: torch.Tensor | None = None, *, expand: bool = False, out: torch.Tensor | None = None) -> torch.Tensor:
         """The effective-action masks of the snapshot rows `rows` (contiguous int64 [n] on the snapshot's device; None = every row, in
         order) -- the launch of `BatchedMultiGridEnv.action_mask()` over the snapshot's own tensors, through the backend of the env
         that took it: a row's masks are the masks that env had when the snapshot was taken.  A row outside [0, rows) leaves its masks
         as they were and is reported by that env's `check_errors()`."""
-        env = self._env() if self._env is not None else None
-        if env is None:
-            raise RuntimeError("action_mask: the env this snapshot was taken from is gone (its backend makes the launch)")
-        env.join()
-        n = self.rows if rows is None else int(env._index_arg("action_mask", "rows", rows).shape[0])
-        mask = _mask_out("action_mask", out, n, self.spec.num_agents, expand, self.device)
-        members = {m: self.tensors.get(m) for m in ("cells", "agents", "aux")}
-        env.backend.action_mask(n, members, self.rows, rows, _lib.MASK_EXPAND if expand else 0, mask, env._bad_words())
-        return mask
-
-    def _distance(self, what: str, rows, query: dict, out, field: bool) -> torch.Tensor:
-        env = self._env() if self._env is not None else None
-        if env is None:
-            raise RuntimeError(f"{what}: the env this snapshot was taken from is gone (its backend makes the launch)")
-        env.join()
-        n = self.rows if rows is None else int(env._index_arg(what, "rows", rows).shape[0])
-        q = _dist_query(what, self.spec, n, self.device, **query)
-        res = _dist_out(what, out, n, self.spec, field, self.device)
-        members = {m: self.tensors.get(m) for m in ("cells", "agents")}
-        env.backend.distance(n, members, self.rows, rows, q, res if field else None, None if field else res, env._bad_words())
-        return res
+        return row_queries.action_mask(self._row_set("action_mask"), rows, expand, out)
 
     def distance_field(self, rows: torch.Tensor | None = None, *, types=None, colors=None, agents=None, points=None, through=(),
                        avoid_lava: bool = False, out: torch.Tensor | None = None) -> torch.Tensor:
@@ -181,94 +161,14 @@ class EnvSnapshot:
         in order) -- the launch of `BatchedMultiGridEnv.distance_field()` over the snapshot's own tensors, through the backend of the
         env that took it.  A row outside [0, rows) leaves its field as it was and is reported by that env's `check_errors()`."""
         query = dict(types=types, colors=colors, agents=agents, points=points, through=through, avoid_lava=avoid_lava)
-        return self._distance("distance_field", rows, query, out, True)
+        return row_queries.distance(self._row_set("distance_field"), rows, query, out, True)
 
     def agent_distance(self, rows: torch.Tensor | None = None, *, types=None, colors=None, agents=None, points=None, through=(),
                        avoid_lava: bool = False, out: torch.Tensor | None = None) -> torch.Tensor:
         """The agents' walking distances in the snapshot rows `rows`: `BatchedMultiGridEnv.agent_distance()` over the snapshot's
         own tensors (see `distance_field()` above)."""
         query = dict(types=types, colors=colors, agents=agents, points=points, through=through, avoid_lava=avoid_lava)
-        return self._distance("agent_distance", rows, query, out, False)
-
-
-def _key_args(what: str, salt, step_count, rng) -> tuple:
-    """(flags, salt) of mgx_state_key / mgx_obs_key"""
-    if isinstance(salt, bool) or not isinstance(salt, int) or not 0 <= salt < 2 ** 64:
-        raise ValueError(f"{what}: salt must be an int in [0, 2**64)")
-    return (_lib.KEY_STEP_COUNT if step_count else 0) | (_lib.KEY_RNG if rng else 0), salt
-
-
-def _key_out(what: str, out, shape: tuple, device) -> torch.Tensor:
-    if out is None:
-        return torch.zeros(shape, dtype=torch.int64, device=device)
-    if not torch.is_tensor(out) or out.dtype is not torch.int64 or tuple(out.shape) != tuple(shape) or out.device != device \
-            or not out.is_contiguous():
-        raise ValueError(f"{what}: out= must be a contiguous int64 tensor of shape {tuple(shape)} on {device}")
-    return out
-
-
-def _mask_out(what: str, out, n: int, A: int, expand: bool, device) -> torch.Tensor:
-    shape, dtype = ((n, A, 7), torch.bool) if expand else ((n, A), torch.uint8)
-    if out is None:
-        return torch.zeros(shape, dtype=dtype, device=device)
-    if not torch.is_tensor(out) or out.dtype is not dtype or tuple(out.shape) != shape or out.device != device or not out.is_contiguous():
-        raise ValueError(f"{what}: out= must be a contiguous {str(dtype).split('.')[-1]} tensor of shape {shape} on {device}")
-    return out
-
-
-_DIST_THROUGH = {"closed": _lib.DIST_THROUGH_CLOSED, "locked": _lib.DIST_THROUGH_LOCKED, "objects": _lib.DIST_THROUGH_OBJECTS}
-
-
-def _dist_bits(what: str, name: str, values, below: int, why: str) -> int:
-    """the bit mask of an iterable of small ints (enum members included)"""
-    if isinstance(values, (str, bytes)) or torch.is_tensor(values):
-        raise ValueError(f"{what}: {name} must be an iterable of ints")
-    mask = 0
-    try:
-        items = list(values)
-    except TypeError:
-        raise ValueError(f"{what}: {name} must be an iterable of ints") from None
-    for v in items:
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < below:
-            raise ValueError(f"{what}: {name} holds {v!r}: {why}")
-        mask |= 1 << int(v)
-    return mask
-
-
-def _dist_query(what: str, spec, n: int, device, types=None, colors=None, agents=None, points=None, through=(), avoid_lava=False) -> dict:
-    """The query of mgx_distance (include/mgx.h "DISTANCE FIELDS": MgxDistance) from the keyword arguments of distance_field() /
-    agent_distance(): {type_mask, colour_mask, agent_mask, flags, points}."""
-    A = spec.num_agents
-    type_mask = 0 if types is None else _dist_bits(what, "types", types, 16, "a Type or an int in [0, 16)")
-    colour_mask = 0xFF if colors is None else _dist_bits(what, "colors", colors, 8, "a Color or an int in [0, 8)")
-    agent_mask = 0 if agents is None else _dist_bits(what, "agents", agents, A, f"an agent index must lie in [0, {A})")
-    if colors is not None and types is None:
-        raise ValueError(f"{what}: colors= narrows the cells that types= selects: pass types= with it")
-    if isinstance(through, str):
-        through = (through,)
-    flags = _lib.DIST_AVOID_LAVA if avoid_lava else 0
-    for w in through:
-        if w not in _DIST_THROUGH:
-            raise ValueError(f"{what}: through= holds {w!r}: it must be a subset of {sorted(_DIST_THROUGH)}")
-        flags |= _DIST_THROUGH[w]
-    if points is not None:
-        if not torch.is_tensor(points) or points.dtype is not torch.int16 or points.dim() != 3 or int(points.shape[0]) != n \
-                or int(points.shape[2]) != 2 or points.device != device or not points.is_contiguous():
-            raise ValueError(f"{what}: points must be a contiguous int16 tensor of shape ({n}, P, 2) on {device}: (x, y) per output row")
-        if int(points.shape[1]) == 0:
-            points = None
-    if not type_mask and not agent_mask and points is None:
-        raise ValueError(f"{what}: the query names no source: pass types=, agents= or points=")
-    return {"type_mask": type_mask, "colour_mask": colour_mask, "agent_mask": agent_mask, "flags": flags, "points": points}
-
-
-def _dist_out(what: str, out, n: int, spec, field: bool, device) -> torch.Tensor:
-    shape = (n, spec.height, spec.width) if field else (n, spec.num_agents)
-    if out is None:
-        return torch.full(shape, -1, dtype=torch.int16, device=device)
-    if not torch.is_tensor(out) or out.dtype is not torch.int16 or tuple(out.shape) != shape or out.device != device or not out.is_contiguous():
-        raise ValueError(f"{what}: out= must be a contiguous int16 tensor of shape {shape} on {device}")
-    return out
+        return row_queries.distance(self._row_set("agent_distance"), rows, query, out, False)
 
 
 class PersistentSession:
@@ -1427,6 +1327,13 @@ class BatchedMultiGridEnv:
         self._bad_words()
         self.join()
 
+    def _row_set(self, what: str) -> RowSet:
+        """This env's live tensors as the rows of a query (row_queries.py)."""
+        self._copy_entry(what)
+        # (`_cells`, not `cells`: reading the grid keeps the layout marker's promises)
+        tensors = {"cells": self._cells, "agents": self.agents, "rng": self.rng, "step_count": self.step_count, "aux": self.aux}
+        return RowSet(what, self, tensors, self.batch, self._cells.device, "env_ids")
+
     def _bad_words(self) -> torch.Tensor:
         """i32[2] on the device: how many pairs / keys / masks the copy, key and mask kernels skipped for an index out of range, and the
         first"""
@@ -1558,14 +1465,7 @@ class BatchedMultiGridEnv:
                  may repeat.  An id outside [0, batch) leaves its key as it was and is reported by `check_errors()`.
         salt     any int in [0, 2**64): another salt gives an independent key (two of them: 128 bits)
         out      an int64 [n] tensor on the env's device to write: a caller that keys every step allocates nothing."""
-        self._copy_entry("state_key")
-        n = self.batch if env_ids is None else int(self._index_arg("state_key", "env_ids", env_ids).shape[0])
-        flags, salt = _key_args("state_key", salt, step_count, rng)
-        keys = _key_out("state_key", out, (n,), self._cells.device)
-        # (`_cells`, not `cells`: reading the grid keeps the layout marker's promises)
-        rows = {"cells": self._cells, "agents": self.agents, "rng": self.rng, "step_count": self.step_count, "aux": self.aux}
-        self.backend.state_key(n, rows, self.batch, env_ids, flags, salt, keys, self._copy_bad)
-        return keys
+        return row_queries.state_key(self._row_set("state_key"), env_ids, salt, step_count, rng, out)
 
     def obs_key(self, obs: torch.Tensor | None = None, dir: torch.Tensor | None = None, *, salt: int = 0,
                 out: torch.Tensor | None = None) -> torch.Tensor:
@@ -1587,7 +1487,7 @@ class BatchedMultiGridEnv:
             raise ValueError(f"obs_key: obs must have shape [..., {v}, {v}, 3] and dir the leading shape [...], got "
                              f"{tuple(obs.shape)} and {tuple(dir.shape)}")
         _, salt = _key_args("obs_key", salt, False, False)
-        keys = _key_out("obs_key", out, tuple(dir.shape), dev)
+        keys = _out("obs_key", out, tuple(dir.shape), torch.int64, 0, dev)
         self.join()
         self.backend.obs_key(int(dir.numel()), obs, dir, salt, keys)
         return keys
@@ -1616,26 +1516,9 @@ class BatchedMultiGridEnv:
                  may repeat.  An id outside [0, batch) leaves its masks as they were and is reported by `check_errors()`.
         out      a uint8 [n, A] (expand: bool [n, A, 7]) tensor on the env's device to write: a caller that masks every step
                  allocates nothing."""
-        self._copy_entry("action_mask")
-        n = self.batch if env_ids is None else int(self._index_arg("action_mask", "env_ids", env_ids).shape[0])
-        mask = _mask_out("action_mask", out, n, self.spec.num_agents, expand, self._cells.device)
-        # (`_cells`, not `cells`: reading the grid keeps the layout marker's promises)
-        rows = {"cells": self._cells, "agents": self.agents, "aux": self.aux}
-        self.backend.action_mask(n, rows, self.batch, env_ids, _lib.MASK_EXPAND if expand else 0, mask, self._copy_bad)
-        return mask
+        return row_queries.action_mask(self._row_set("action_mask"), env_ids, expand, out)
 
     # ------------------------------------------------------------------------------------------ distance fields
-    def _distance(self, what: str, env_ids, query: dict, out, field: bool) -> torch.Tensor:
-        self._copy_entry(what)
-        n = self.batch if env_ids is None else int(self._index_arg(what, "env_ids", env_ids).shape[0])
-        dev = self._cells.device
-        q = _dist_query(what, self.spec, n, dev, **query)
-        res = _dist_out(what, out, n, self.spec, field, dev)
-        # (`_cells`, not `cells`: reading the grid keeps the layout marker's promises)
-        rows = {"cells": self._cells, "agents": self.agents}
-        self.backend.distance(n, rows, self.batch, env_ids, q, res if field else None, None if field else res, self._copy_bad)
-        return res
-
     def distance_field(self, env_ids: torch.Tensor | None = None, *, types=None, colors=None, agents=None, points=None, through=(),
                        avoid_lava: bool = False, out: torch.Tensor | None = None) -> torch.Tensor:
         """How many moves every cell of the envs `env_ids` lies from the nearest source cell, walls respected (include/mgx.h
@@ -1656,7 +1539,7 @@ class BatchedMultiGridEnv:
         out         an int16 [n, H, W] tensor on the env's device to write: a caller that asks every step allocates nothing.
         Sides above 64 are refused (the kernel holds a grid row in one 64-bit word, an env's rows in one wavefront)."""
         query = dict(types=types, colors=colors, agents=agents, points=points, through=through, avoid_lava=avoid_lava)
-        return self._distance("distance_field", env_ids, query, out, True)
+        return row_queries.distance(self._row_set("distance_field"), env_ids, query, out, True)
 
     def agent_distance(self, env_ids: torch.Tensor | None = None, *, types=None, colors=None, agents=None, points=None, through=(),
                        avoid_lava: bool = False, out: torch.Tensor | None = None) -> torch.Tensor:
@@ -1664,7 +1547,7 @@ class BatchedMultiGridEnv:
         [n, A], the number of moves from agent a to the nearest source, -1 when there is no way (or the agent row lies outside the
         grid).  A terminated agent is answered like any other.  `out`: an int16 [n, A] tensor to write."""
         query = dict(types=types, colors=colors, agents=agents, points=points, through=through, avoid_lava=avoid_lava)
-        return self._distance("agent_distance", env_ids, query, out, False)
+        return row_queries.distance(self._row_set("agent_distance"), env_ids, query, out, False)
 
     def outputs_to_host(self) -> dict:
         """Everything the last step / gen_obs handed back, on the host after ONE device-to-host copy (into a pinned buffer) and one

@@ -36,8 +36,10 @@ UNITS = ([("mgx_kernels", os.path.join(CSRC, "mgx_kernels.hip"), ()), ("mgx_aux"
           ("mgx_key_table", os.path.join(CSRC, "mgx_key_table.hip"), ())]
          + [(f"mgx_fused_v{v}", os.path.join(CSRC, "mgx_fused_inst.hip"), (f"MGX_INST_V={v}",)) for v in VIEWS])
 SRCS = sorted({u[1] for u in UNITS})
-DEPS = SRCS + [os.path.join(CSRC, "mgx_action_mask.h"), os.path.join(CSRC, "mgx_aux_geom.h"), os.path.join(CSRC, "mgx_distance.h"), os.path.join(CSRC, "mgx_fused.h"), os.path.join(CSRC, "mgx_fused_body.inc"), os.path.join(CSRC, "mgx_host.h"), os.path.join(CSRC, "mgx_key_table.h"), os.path.join(CSRC, "mgx_layout_gen.h"), os.path.join(CSRC, "mgx_rules.h"),
-               os.path.join(CSRC, "mgx_render.h"), os.path.join(CSRC, "mgx_state_key.h"), os.path.join(ROOT, "include", "mgx.h")]
+#: everything the library is compiled from: the units, every header and .inc beside them (listed, not named by hand: a header
+#: missing here would make stale() reuse an old library without saying so), and the public header
+DEPS = (SRCS + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc")))
+        + [os.path.join(ROOT, "include", "mgx.h")])
 LIB = os.path.join(HERE, "lib", "libmgx.so")
 LIB_DBG = os.path.join(HERE, "lib", "libmgx_dbg.so")
 LIB_CHK = os.path.join(HERE, "lib", "libmgx_chk.so")

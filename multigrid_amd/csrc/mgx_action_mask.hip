@@ -13,7 +13,7 @@
 //                           has a hook that matters.  Output: one byte per lane (consecutive lanes, consecutive bytes), or with
 //                           MGX_MASK_EXPAND the env's 7 * A bytes in rounds of `group` consecutive bytes, byte t taking agent t / 7's
 //                           mask from its lane by a __shfl.  Byte stores: the output may start at any address.  No LDS, no
-//                           inter-wavefront traffic but the two `bad` words (plain atomicAdd / atomicMin).
+//                           inter-wavefront traffic but the two `bad` words (mgx_env_rows.h: count_bad).
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
@@ -42,22 +42,13 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 template <int CB>
 __global__ __launch_bounds__(64 * kMaskWpb) void action_mask_kernel(const ActionMaskArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t p0 = ((int64_t)blockIdx.x * kMaskWpb + wave) * (64 >> a.group_shift);
-    if (p0 >= a.n) return;                                        // (wave-uniform: the lanes below stay together through the shuffles)
-    const int k = lane & (a.group - 1), first = lane - k;         // the agent of this lane; lane 0 of its group
-    const int64_t i = p0 + (lane >> a.group_shift);
+    const RowWave w = row_wave<kMaskWpb>(64 >> a.group_shift);
+    if (w.p0 >= a.n) return;                                      // (the lanes below stay together through the shuffles)
+    const int lane = w.lane, k = lane & (a.group - 1), first = lane - k;     // the agent of this lane; lane 0 of its group
+    const int64_t i = w.p0 + (lane >> a.group_shift);
     int64_t s = 0;
     bool ok = false;
-    if (i < a.n) {
-        s = a.src_idx ? a.src_idx[i] : i;
-        ok = s >= 0 && s < a.rows;
-        if (!ok && k == 0 && a.bad) {                             // its bytes are left alone, and counted (mgx_state_key's convention)
-            atomicAdd(a.bad, 1);
-            atomicMin(a.bad + 1, (int32_t)(i < INT_MAX ? i : INT_MAX));
-        }
-    }
+    if (i < a.n) ok = pick_row(a.src_idx, i, a.rows, k == 0, a.bad, s);      // (a bad index: its bytes are left alone)
     const bool mine = ok && k < a.A;
     uint64_t row = 0;
     if (mine) row = reinterpret_cast<const uint64_t *>(a.agents)[s * a.A + k];
@@ -98,30 +89,19 @@ __global__ __launch_bounds__(64 * kMaskWpb) void action_mask_kernel(const Action
     }
 }
 
-int log2_of(int pow2) {
-    int s = 0;
-    while ((1 << s) < pow2) ++s;
-    return s;
-}
-
 }  // namespace
 
 extern "C" {
 
 int mgx_action_mask(const MgxSpec *spec, int64_t n, const MgxEnvRows *src, const int64_t *src_idx, uint32_t flags, uint8_t *mask,
                     int32_t *bad, void *stream) {
-    if (!spec || n < 0 || !src) return MGX_ERR_INVALID_ARGUMENT;
-    if (spec->num_agents < 1 || spec->num_agents > MGX_MAX_AGENTS || spec->width < 1 || spec->height < 1 || spec->cell_bytes < 0
-        || spec->cell_bytes > 3)
-        return MGX_ERR_INVALID_ARGUMENT;
+    if (check_rows_spec(spec) || n < 0 || !src) return MGX_ERR_INVALID_ARGUMENT;
     if (src->rows < 0 || (flags & ~(uint32_t)MGX_MASK_EXPAND)) return MGX_ERR_INVALID_ARGUMENT;
     if (n == 0) return MGX_OK;
-    if (!src->cells || !src->agents || !mask) return MGX_ERR_INVALID_ARGUMENT;
-    const int cb = spec->cell_bytes == 1 ? 1 : (spec->cell_bytes == 3 ? 3 : 2);
-    if (misaligned(src->aux, 16) || misaligned(src->agents, 8) || (cb == 2 && misaligned(src->cells, 2)) || misaligned(src_idx, 8)
-        || misaligned(bad, 4))
-        return MGX_ERR_INVALID_ARGUMENT;
-    if (n > (int64_t)INT_MAX * 64 * kMaskWpb) return MGX_ERR_UNSUPPORTED;
+    const int cb = cell_bytes(spec->cell_bytes);
+    const uint32_t read = ROWS_CELLS | ROWS_AGENTS;
+    if (check_rows(*src, read, read | ROWS_AUX, cb) || !mask) return MGX_ERR_INVALID_ARGUMENT;
+    if (const int rc = check_rows_n(n, src_idx, bad, kMaskWpb)) return rc;
     const int64_t cells = (int64_t)spec->width * spec->height;
     if (cells > 2 * 65536) return MGX_ERR_UNSUPPORTED;            // (mgx_state_key's bound: a cell's byte offset fits an int)
     const ActionMaskGeom g = action_mask_geom(spec->num_agents, n);
@@ -129,8 +109,8 @@ int mgx_action_mask(const MgxSpec *spec, int64_t n, const MgxEnvRows *src, const
     const ActionMaskArgs args{n, src->rows, g.group, log2_of(g.group), spec->num_agents, spec->width, spec->height, spec->env_kind,
                               spec->allow_agent_overlap, (int32_t)(flags & MGX_MASK_EXPAND), cells * cb,
                               reinterpret_cast<const uint8_t *>(src->cells), src->agents, src->aux, src_idx, mask, bad};
-    void (*kernel)(const ActionMaskArgs) = cb == 1 ? action_mask_kernel<1> : (cb == 3 ? action_mask_kernel<3> : action_mask_kernel<2>);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)g.blocks), dim3(64 * kMaskWpb), 0, static_cast<hipStream_t>(stream), args);
+    hipLaunchKernelGGL(MGX_BY_CELL_BYTES(action_mask_kernel, cb), dim3((unsigned)g.blocks), dim3(64 * kMaskWpb), 0,
+                       static_cast<hipStream_t>(stream), args);
     return finish_launch();
 }
 

@@ -722,7 +722,7 @@ int check_reset_pool(const MgxSpec *spec, int64_t batch, const MgxAutoReset &poo
         || ((spec->cell_bytes == 0 || spec->cell_bytes == 2) && (misaligned(grid, 2) || misaligned(pool.pool_grid, 2))))
         return MGX_ERR_INVALID_ARGUMENT;
     if (spec->cell_bytes < 0 || spec->cell_bytes > 3) return MGX_ERR_INVALID_ARGUMENT;
-    pl.HWB = spec->width * spec->height * (spec->cell_bytes == 1 ? 1 : (spec->cell_bytes == 3 ? 3 : kCellBytes));
+    pl.HWB = spec->width * spec->height * cell_bytes(spec->cell_bytes);
     const int64_t blocks = (batch + 255) / 256;
     if (blocks > INT_MAX) return MGX_ERR_UNSUPPORTED;
     pl.blocks = dim3((unsigned)blocks);
@@ -796,7 +796,7 @@ int mgx_full_obs(const MgxSpec *spec, int64_t batch, const MgxCell *grid, const 
     if (spec->width > 255 || spec->height > 255) return MGX_ERR_UNSUPPORTED;
     const int HW = spec->width * spec->height;
     if (spec->cell_bytes < 0 || spec->cell_bytes > 3) return MGX_ERR_INVALID_ARGUMENT;
-    const int cb = spec->cell_bytes == 1 ? 1 : (spec->cell_bytes == 3 ? 3 : kCellBytes);
+    const int cb = cell_bytes(spec->cell_bytes);
     if (!full_obs_fits(spec->width, spec->height, cb)) return MGX_ERR_UNSUPPORTED;
     if (batch == 0) return MGX_OK;
     if (!grid || !agents || !out || misaligned(agents, 8) || misaligned(grid, 16) || misaligned(out, 16))

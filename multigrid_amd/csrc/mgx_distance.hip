@@ -20,7 +20,7 @@
 //              addresses, any 2-byte alignment.
 //     agents   lane a < A of a group reads agent row a, fetches the words of row y and takes bit x; in rounds of `group` agents
 //              when there are more agents than lanes.
-//   No LDS, no inter-wavefront traffic but the two `bad` words (plain atomicAdd / atomicMin).
+//   No LDS, no inter-wavefront traffic but the two `bad` words (mgx_env_rows.h: count_bad).
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
@@ -61,25 +61,18 @@ __device__ __forceinline__ int16_t assemble(const uint64_t vis, const uint64_t (
 
 template <int CB>
 __global__ __launch_bounds__(64 * kDistWpb) void distance_kernel(const DistanceArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int per = 64 >> a.group_shift;
-    const int64_t p0 = ((int64_t)blockIdx.x * kDistWpb + wave) * per;
-    if (p0 >= a.n) return;                                        // (wave-uniform: the lanes below stay together through the shuffles)
+    const RowWave w = row_wave<kDistWpb>(per);
+    if (w.p0 >= a.n) return;                                      // (the lanes below stay together through the shuffles)
+    const int lane = w.lane;
+    const int64_t p0 = w.p0;
     const int W = a.W, H = a.H, A = a.A;
     const int r = lane & (a.group - 1), first = lane - r;         // the grid row of this lane; lane 0 of its group
     const int mine = lane >> a.group_shift;                       // the env of this lane, within the wavefront
     const int64_t i = p0 + mine;
     int64_t s = 0;
     bool ok = false;
-    if (i < a.n) {
-        s = a.src_idx ? a.src_idx[i] : i;
-        ok = s >= 0 && s < a.rows;
-        if (!ok && r == 0 && a.bad) {                             // its rows are left alone, and counted (mgx_action_mask's convention)
-            atomicAdd(a.bad, 1);
-            atomicMin(a.bad + 1, (int32_t)(i < INT_MAX ? i : INT_MAX));
-        }
-    }
+    if (i < a.n) ok = pick_row(a.src_idx, i, a.rows, r == 0, a.bad, s);      // (a bad index: its output rows are left alone)
     const uint64_t okmask = __ballot(ok);                         // bit e << group_shift: env e of the wavefront has a row to read
 
     // ---- load: 64 / wp rows per round; lane (ly, lx) of a round classifies cell (y0 + ly, lx)
@@ -171,39 +164,29 @@ __global__ __launch_bounds__(64 * kDistWpb) void distance_kernel(const DistanceA
     }
 }
 
-int log2_of(int pow2) {
-    int s = 0;
-    while ((1 << s) < pow2) ++s;
-    return s;
-}
-
 }  // namespace
 
 extern "C" {
 
 int mgx_distance(const MgxSpec *spec, int64_t n, const MgxEnvRows *src, const int64_t *src_idx, const MgxDistance *q, int16_t *field,
                  int16_t *agent_dist, int32_t *bad, void *stream) {
-    if (!spec || n < 0 || !src) return MGX_ERR_INVALID_ARGUMENT;
-    if (spec->num_agents < 1 || spec->num_agents > MGX_MAX_AGENTS || spec->width < 1 || spec->height < 1 || spec->cell_bytes < 0
-        || spec->cell_bytes > 3)
-        return MGX_ERR_INVALID_ARGUMENT;
+    if (check_rows_spec(spec) || n < 0 || !src) return MGX_ERR_INVALID_ARGUMENT;
     if (src->rows < 0 || !q || (q->flags & ~kDistFlags) || q->num_points < 0) return MGX_ERR_INVALID_ARGUMENT;
     if (n == 0) return MGX_OK;
-    if (!src->cells || !src->agents || (!field && !agent_dist) || (q->num_points > 0 && !q->points)) return MGX_ERR_INVALID_ARGUMENT;
-    const int cb = spec->cell_bytes == 1 ? 1 : (spec->cell_bytes == 3 ? 3 : 2);
-    if (misaligned(field, 2) || misaligned(agent_dist, 2) || misaligned(q->points, 2) || (cb == 2 && misaligned(src->cells, 2))
-        || misaligned(src->agents, 8) || misaligned(src_idx, 8) || misaligned(bad, 4))
-        return MGX_ERR_INVALID_ARGUMENT;
+    const int cb = cell_bytes(spec->cell_bytes);
+    const uint32_t read = ROWS_CELLS | ROWS_AGENTS;
+    if (check_rows(*src, read, read, cb) || (!field && !agent_dist) || (q->num_points > 0 && !q->points)) return MGX_ERR_INVALID_ARGUMENT;
+    if (misaligned(field, 2) || misaligned(agent_dist, 2) || misaligned(q->points, 2)) return MGX_ERR_INVALID_ARGUMENT;
+    if (const int rc = check_rows_n(n, src_idx, bad, kDistWpb)) return rc;
     if (spec->width > kDistMaxSide || spec->height > kDistMaxSide) return MGX_ERR_UNSUPPORTED;   // (a lane per row, a bit per column)
-    if (n > (int64_t)INT_MAX * 64 * kDistWpb) return MGX_ERR_UNSUPPORTED;
     const DistanceGeom g = distance_geom(spec->width, spec->height, n);
     if (g.blocks > INT_MAX) return MGX_ERR_UNSUPPORTED;
     const DistanceArgs args{n, src->rows, g.group, log2_of(g.group), log2_of(g.wp), spec->num_agents, spec->width, spec->height,
                             q->type_mask, q->colour_mask, q->agent_mask, q->flags, q->num_points,
                             (int64_t)spec->width * spec->height * cb, reinterpret_cast<const uint8_t *>(src->cells), src->agents, src_idx,
                             q->num_points > 0 ? q->points : nullptr, field, agent_dist, bad};
-    void (*kernel)(const DistanceArgs) = cb == 1 ? distance_kernel<1> : (cb == 3 ? distance_kernel<3> : distance_kernel<2>);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)g.blocks), dim3(64 * kDistWpb), 0, static_cast<hipStream_t>(stream), args);
+    hipLaunchKernelGGL(MGX_BY_CELL_BYTES(distance_kernel, cb), dim3((unsigned)g.blocks), dim3(64 * kDistWpb), 0,
+                       static_cast<hipStream_t>(stream), args);
     return finish_launch();
 }
 

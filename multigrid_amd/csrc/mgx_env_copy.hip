@@ -13,7 +13,7 @@
 //                           per lane, every load of a round issued before its stores.  Tiles of 64 vectors or more go pair by pair,
 //                           lanes over the vectors; smaller ones as (pair, vector) items flattened over the lanes, the pair found
 //                           by recip32 (units == 1 has no 32-bit reciprocal: it branches, as copy_layouts does).
-//                           No inter-wavefront traffic but the two `bad` words (plain atomicAdd / atomicMin).
+//                           No inter-wavefront traffic but the two `bad` words (mgx_env_rows.h: count_bad).
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
@@ -96,21 +96,16 @@ __device__ __forceinline__ void zero_rows(int m, int units, uint32_t inv_units, 
 template <typename VecT>
 __global__ __launch_bounds__(64 * kEnvCopyWpb) void env_copy_kernel(const EnvCopyArgs a) {
     __shared__ int64_t s_src[kEnvCopyWpb][64], s_dst[kEnvCopyWpb][64];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t p0 = ((int64_t)blockIdx.x * kEnvCopyWpb + wave) * a.run;
-    if (p0 >= a.n) return;
-    const int64_t i = p0 + lane;
+    const RowWave w = row_wave<kEnvCopyWpb>(a.run);
+    if (w.p0 >= a.n) return;
+    const int lane = w.lane, wave = w.wave;
+    const int64_t i = w.p0 + lane;
     int64_t s = 0, d = 0;
     bool ok = false;
     if (lane < a.run && i < a.n) {
-        s = a.src_idx ? a.src_idx[i] : i;
-        d = a.dst_idx ? a.dst_idx[i] : i;
-        ok = s >= 0 && s < a.src.rows && d >= 0 && d < a.dst.rows;
-        if (!ok && a.bad) {                                               // skipped whole, and counted (the step's `err` convention)
-            atomicAdd(a.bad, 1);
-            atomicMin(a.bad + 1, (int32_t)(i < INT_MAX ? i : INT_MAX));
-        }
+        const bool ok_s = pick_row(a.src_idx, i, a.src.rows, s), ok_d = pick_row(a.dst_idx, i, a.dst.rows, d);
+        ok = ok_s && ok_d;
+        if (!ok) count_bad(a.bad, i);                                     // the PAIR is skipped whole, and counted once
     }
     if (ok) {
         // the pair's small rows: what both sets carry, every load before the first store
@@ -177,16 +172,11 @@ __global__ __launch_bounds__(64 * kEnvCopyWpb) void env_copy_kernel(const EnvCop
     ((unit) == 16 ? env_copy_kernel<u32x4> : (unit) == 8 ? env_copy_kernel<uint64_t> : (unit) == 4 ? env_copy_kernel<uint32_t> \
      : (unit) == 2 ? env_copy_kernel<uint16_t> : env_copy_kernel<uint8_t>)
 
-// a state set's required members, its trio (all or none) and its alignments (as check_stats, mgx_stats.hip)
-int check_rows(const MgxSpec *spec, const MgxEnvRows *r) {
-    if (!r->cells || !r->agents || !r->rng || !r->step_count) return MGX_ERR_INVALID_ARGUMENT;
-    const int trio = (r->cur_return != nullptr) + (r->cur_length != nullptr) + (r->over != nullptr);
+// a state set that is copied: every member moves, and the running trio is there whole or not at all
+int check_copied(const MgxEnvRows &r, int cb) {
+    const int trio = (r.cur_return != nullptr) + (r.cur_length != nullptr) + (r.over != nullptr);
     if (trio != 0 && trio != 3) return MGX_ERR_INVALID_ARGUMENT;
-    if (misaligned(r->rng, 16) || misaligned(r->aux, 16) || misaligned(r->gen_state, 16) || misaligned(r->agents, 8)
-        || misaligned(r->cur_return, 8) || misaligned(r->step_count, 4) || misaligned(r->marker, 4) || misaligned(r->episode, 4)
-        || misaligned(r->cur_length, 4) || ((spec->cell_bytes == 0 || spec->cell_bytes == 2) && misaligned(r->cells, 2)))
-        return MGX_ERR_INVALID_ARGUMENT;
-    return MGX_OK;
+    return check_rows(r, ROWS_CELLS | ROWS_AGENTS | ROWS_RNG | ROWS_STEP_COUNT, ROWS_ALL, cb);
 }
 
 }  // namespace
@@ -195,17 +185,14 @@ extern "C" {
 
 int mgx_env_copy(const MgxSpec *spec, int64_t n, const MgxEnvRows *src, const int64_t *src_idx, const MgxEnvRows *dst,
                  const int64_t *dst_idx, int32_t *stage_tag, int32_t stage_mode, int32_t marker_fill, int32_t *bad, void *stream) {
-    if (!spec || n < 0 || !src || !dst) return MGX_ERR_INVALID_ARGUMENT;
-    if (spec->num_agents < 1 || spec->num_agents > MGX_MAX_AGENTS || spec->width < 1 || spec->height < 1 || spec->cell_bytes < 0
-        || spec->cell_bytes > 3)
-        return MGX_ERR_INVALID_ARGUMENT;
+    if (check_rows_spec(spec) || n < 0 || !src || !dst) return MGX_ERR_INVALID_ARGUMENT;
     if (src->rows < 0 || dst->rows < 0 || stage_mode < 0 || stage_mode > 2) return MGX_ERR_INVALID_ARGUMENT;
     if (n == 0) return MGX_OK;
-    if (const int rc = check_rows(spec, src)) return rc;
-    if (const int rc = check_rows(spec, dst)) return rc;
-    if (misaligned(src_idx, 8) || misaligned(dst_idx, 8) || misaligned(stage_tag, 16) || misaligned(bad, 4)) return MGX_ERR_INVALID_ARGUMENT;
-    if (n > (int64_t)INT_MAX * 64 * kEnvCopyWpb) return MGX_ERR_UNSUPPORTED;
-    const int tile_bytes = spec->width * spec->height * (spec->cell_bytes == 1 ? 1 : (spec->cell_bytes == 3 ? 3 : MGX_CELL_BYTES));
+    const int cb = cell_bytes(spec->cell_bytes);
+    if (check_copied(*src, cb) || check_copied(*dst, cb) || misaligned(dst_idx, 8) || misaligned(stage_tag, 16))
+        return MGX_ERR_INVALID_ARGUMENT;
+    if (const int rc = check_rows_n(n, src_idx, bad, kEnvCopyWpb)) return rc;
+    const int tile_bytes = spec->width * spec->height * cb;
     const EnvCopyGeom g = env_copy_geom(tile_bytes, n);
     if (g.blocks > INT_MAX) return MGX_ERR_UNSUPPORTED;
     // widest copy unit that divides the tile size and both base addresses (mgx_aux_geom.h)

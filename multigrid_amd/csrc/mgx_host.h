@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/mgx.h"
+#include "mgx_env_rows.h"      // misaligned(), cell_bytes(), log2_of(): no HIP needed
 
 extern "C" void mgx_internal_set_hip_error(int e);      // mgx_kernels.hip: what mgx_last_hip_error() reports
 
@@ -17,8 +18,6 @@ inline int finish_launch() {
     if (e != hipSuccess) { mgx_internal_set_hip_error((int)e); return MGX_ERR_LAUNCH; }
     return MGX_OK;
 }
-
-inline bool misaligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }     // (NULL is aligned)
 
 }  // namespace mgx
 

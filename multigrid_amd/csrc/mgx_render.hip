@@ -156,7 +156,7 @@ int mgx_render(const MgxSpec *spec, int64_t n, const MgxCell *grid, const uint8_
     const int W = spec->width, H = spec->height, A = spec->num_agents, v = spec->view_size;
     if (W < 3 || H < 3 || W > 255 || H > 255 || A < 1 || A > MGX_MAX_AGENTS || v < 3 || (v & 1) == 0) return MGX_ERR_INVALID_ARGUMENT;
     if (spec->cell_bytes < 0 || spec->cell_bytes > 3) return MGX_ERR_INVALID_ARGUMENT;
-    const int cb = spec->cell_bytes == 1 ? 1 : (spec->cell_bytes == 3 ? 3 : kCellBytes);
+    const int cb = cell_bytes(spec->cell_bytes);
     if (n == 0) return MGX_OK;
     if (!grid || !agents || !atlas || !frames || (cb == 2 && misaligned(grid, 2))) return MGX_ERR_INVALID_ARGUMENT;
     if (n * H > INT_MAX) return MGX_ERR_UNSUPPORTED;

@@ -59,9 +59,6 @@ MGX_HD uint32_t key_le32(const uint8_t *p) {
     return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
 }
 
-// bytes per cell of MgxSpec.cell_bytes (0 and 2: the 16-bit cells)
-MGX_HD int key_cell_bytes(int spec_cell_bytes) { return spec_cell_bytes == 1 ? 1 : (spec_cell_bytes == 3 ? 3 : 2); }
-
 // cell p of a grid of `cb`-byte cells, canonical
 MGX_HD uint32_t key_cell_at(int cb, const uint8_t *cells, int p) {
     if (cb == 1) return key_cell8(cells[p]);

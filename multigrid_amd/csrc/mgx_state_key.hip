@@ -15,7 +15,7 @@
 //                           table look-ups (key_quad8).  Then the env's small words (agent rows, aux, step count, rng: one
 //                           dword load each) the same way.  The lanes' partial keys meet in an XOR butterfly over the group
 //                           (__shfl_xor: XOR makes the order free), and the group's first lane stores the 8 bytes.  No LDS, no
-//                           inter-wavefront traffic but the two `bad` words (plain atomicAdd / atomicMin).
+//                           inter-wavefront traffic but the two `bad` words (mgx_env_rows.h: count_bad).
 //   obs_key_kernel          keys of n views u8[v,v,3] + their directions, the same way: a group of lanes (obs_key_group) per view,
 //                           lane k takes the view's dwords k, k + group, ...  A view row is 3 * v * v bytes, so it is dword-aligned
 //                           only every fourth view: the whole dwords are loaded at byte alignment (gfx950 serves a misaligned
@@ -146,22 +146,13 @@ __device__ __forceinline__ uint64_t group_xor(uint64_t x, int group) {
 template <int CB, typename VecT>
 __global__ __launch_bounds__(64 * kKeyWpb) void state_key_kernel(const StateKeyArgs a) {
     using K = KeyChunk<CB, VecT>;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t p0 = ((int64_t)blockIdx.x * kKeyWpb + wave) * a.run;
-    if (p0 >= a.n) return;                                        // (wave-uniform: the lanes below stay together up to the butterfly)
-    const int e = lane >> a.group_shift, k = lane & (a.group - 1);
-    const int64_t i = p0 + e;
+    const RowWave w = row_wave<kKeyWpb>(a.run);
+    if (w.p0 >= a.n) return;                                      // (the lanes below stay together up to the butterfly)
+    const int e = w.lane >> a.group_shift, k = w.lane & (a.group - 1);
+    const int64_t i = w.p0 + e;
     int64_t s = 0;
     bool ok = false;
-    if (e < a.run && i < a.n) {
-        s = a.src_idx ? a.src_idx[i] : i;
-        ok = s >= 0 && s < a.src.rows;
-        if (!ok && k == 0 && a.bad) {                             // its key is left alone, and counted (mgx_env_copy's convention)
-            atomicAdd(a.bad, 1);
-            atomicMin(a.bad + 1, (int32_t)(i < INT_MAX ? i : INT_MAX));
-        }
-    }
+    if (e < a.run && i < a.n) ok = pick_row(a.src_idx, i, a.src.rows, k == 0, a.bad, s);   // (a bad index: its key is left alone)
     uint64_t key = 0;
     if (ok) {
         const uint8_t *tile = reinterpret_cast<const uint8_t *>(a.src.cells) + s * a.tile_bytes;
@@ -211,12 +202,10 @@ __device__ __forceinline__ uint32_t load_view_word(const uint8_t *img, int j, in
 
 template <bool BYTES>
 __global__ __launch_bounds__(64 * kKeyWpb) void obs_key_kernel(const ObsKeyArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t v0 = ((int64_t)blockIdx.x * kKeyWpb + wave) * (64 >> a.group_shift);
-    if (v0 >= a.n) return;
-    const int k = lane & (a.group - 1);
-    const int64_t i = v0 + (lane >> a.group_shift);
+    const RowWave w = row_wave<kKeyWpb>(64 >> a.group_shift);
+    if (w.p0 >= a.n) return;
+    const int k = w.lane & (a.group - 1);
+    const int64_t i = w.p0 + (w.lane >> a.group_shift);
     const bool ok = i < a.n;
     uint64_t key = 0;
     if (ok) {
@@ -235,12 +224,6 @@ __global__ __launch_bounds__(64 * kKeyWpb) void obs_key_kernel(const ObsKeyArgs 
     }
     key = group_xor(key, a.group);
     if (ok && k == 0) a.keys[i] = (int64_t)key;
-}
-
-int log2_of(int pow2) {
-    int s = 0;
-    while ((1 << s) < pow2) ++s;
-    return s;
 }
 
 typedef void (*StateKeyKernel)(const StateKeyArgs);
@@ -293,18 +276,13 @@ int mgx_debug_stream_read(const void *p, int64_t bytes, uint32_t *out, void *str
 
 int mgx_state_key(const MgxSpec *spec, int64_t n, const MgxEnvRows *src, const int64_t *src_idx, uint32_t flags, uint64_t salt,
                   int64_t *keys, int32_t *bad, void *stream) {
-    if (!spec || n < 0 || !src) return MGX_ERR_INVALID_ARGUMENT;
-    if (spec->num_agents < 1 || spec->num_agents > MGX_MAX_AGENTS || spec->width < 1 || spec->height < 1 || spec->cell_bytes < 0
-        || spec->cell_bytes > 3)
-        return MGX_ERR_INVALID_ARGUMENT;
+    if (check_rows_spec(spec) || n < 0 || !src) return MGX_ERR_INVALID_ARGUMENT;
     if (src->rows < 0 || (flags & ~(uint32_t)(MGX_KEY_STEP_COUNT | MGX_KEY_RNG))) return MGX_ERR_INVALID_ARGUMENT;
     if (n == 0) return MGX_OK;
-    if (!src->cells || !src->agents || !src->rng || !src->step_count || !keys) return MGX_ERR_INVALID_ARGUMENT;
-    const int cb = key_cell_bytes(spec->cell_bytes);
-    if (misaligned(src->rng, 16) || misaligned(src->aux, 16) || misaligned(src->agents, 8) || misaligned(src->step_count, 4)
-        || (cb == 2 && misaligned(src->cells, 2)) || misaligned(src_idx, 8) || misaligned(keys, 8) || misaligned(bad, 4))
-        return MGX_ERR_INVALID_ARGUMENT;
-    if (n > (int64_t)INT_MAX * 64 * kKeyWpb) return MGX_ERR_UNSUPPORTED;
+    const int cb = cell_bytes(spec->cell_bytes);
+    const uint32_t read = ROWS_CELLS | ROWS_AGENTS | ROWS_RNG | ROWS_STEP_COUNT;
+    if (check_rows(*src, read, read | ROWS_AUX, cb) || !keys || misaligned(keys, 8)) return MGX_ERR_INVALID_ARGUMENT;
+    if (const int rc = check_rows_n(n, src_idx, bad, kKeyWpb)) return rc;
     const int64_t cells = (int64_t)spec->width * spec->height;
     if (cells > 2 * 65536) return MGX_ERR_UNSUPPORTED;            // (a cell word's index is 16 bits wide)
     const int HW = (int)cells, tile_bytes = HW * cb;

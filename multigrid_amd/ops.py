@@ -572,28 +572,28 @@ class HipBackend(KeyTableOps):
         """rows = {member: tensor or None} of include/mgx.h MgxEnvRows (missing = None), `n` = the rows the set holds"""
         return _lib.MgxEnvRows(*[_ptr(rows.get(m)) for m, _ in _lib.MgxEnvRows._fields_[:-1]], n)
 
+    def _row_query(self, fn: str, dev, n, rows, n_rows, idx, mine: tuple, bad):
+        """The one call path of the launchers that read chosen rows of a state set (csrc/mgx_env_rows.h), on torch's current stream
+        of `dev`: fn(spec, n, `rows` as MgxEnvRows, idx, *mine, bad, stream) -- `mine` is what the call has beside that."""
+        s = self._env_rows(rows, n_rows)
+        with torch.cuda.device(dev):
+            rc = getattr(_lib.lib(), fn)(C.byref(self.sc), n, C.byref(s), _ptr(idx), *mine, _ptr(bad), _stream(dev))
+        _lib.check(rc, fn)
+
     def env_copy(self, n, src, src_rows, src_idx, dst, dst_rows, dst_idx, stage_tag, stage_mode, marker_fill, bad):
         """mgx_env_copy on torch's current stream: for i < n, row src_idx[i] of the state set `src` (a dict of tensors, `src_rows`
         rows) -> row dst_idx[i] of `dst`; the index tensors (i64[n] on the device, None = the identity) are read by the kernel as
         they are.  `stage_tag` / `stage_mode`: the destination's staging tags (or None / _lib.STAGE_NONE); `bad` i32[2]."""
-        s, d = self._env_rows(src, src_rows), self._env_rows(dst, dst_rows)
-        dev = dst["cells"].device
-        with torch.cuda.device(dev):
-            rc = _lib.lib().mgx_env_copy(C.byref(self.sc), n, C.byref(s), _ptr(src_idx), C.byref(d), _ptr(dst_idx), _ptr(stage_tag),
-                                         stage_mode, int(bool(marker_fill)), _ptr(bad), _stream(dev))
-        _lib.check(rc, "mgx_env_copy")
+        d = self._env_rows(dst, dst_rows)
+        mine = (C.byref(d), _ptr(dst_idx), _ptr(stage_tag), stage_mode, int(bool(marker_fill)))
+        self._row_query("mgx_env_copy", dst["cells"].device, n, src, src_rows, src_idx, mine, bad)
 
     # ------------------------------------------------------------------------------------------ state / observation keys
     def state_key(self, n, rows, n_rows, idx, flags, salt, keys, bad):
         """mgx_state_key on torch's current stream: keys[i] (i64[n]) = the key of row idx[i] of the state set `rows` (a dict of
         tensors holding `n_rows` rows; idx: i64[n] on the device, None = the identity, read by the kernel as it is).  `flags`:
         _lib.KEY_STEP_COUNT | _lib.KEY_RNG; `salt`: an int in [0, 2**64); `bad` i32[2] or None."""
-        s = self._env_rows(rows, n_rows)
-        dev = keys.device
-        with torch.cuda.device(dev):
-            rc = _lib.lib().mgx_state_key(C.byref(self.sc), n, C.byref(s), _ptr(idx), flags, salt, keys.data_ptr(), _ptr(bad),
-                                          _stream(dev))
-        _lib.check(rc, "mgx_state_key")
+        self._row_query("mgx_state_key", keys.device, n, rows, n_rows, idx, (flags, salt, keys.data_ptr()), bad)
 
     def obs_key(self, n, obs, dir, salt, keys):
         """mgx_obs_key on torch's current stream: keys[i] (i64[n]) = the key of view i of obs u8[n,v,v,3] / dir u8[n]."""
@@ -607,11 +607,7 @@ class HipBackend(KeyTableOps):
         """mgx_action_mask on torch's current stream: mask[i] (u8[n,A], or u8[n,A,7] of 0 / 1 with _lib.MASK_EXPAND in `flags`) = the
         effective-action masks of row idx[i] of the state set `rows` (a dict of tensors holding `n_rows` rows: cells, agents, aux;
         idx: i64[n] on the device, None = the identity, read by the kernel as it is).  `bad` i32[2] or None."""
-        s = self._env_rows(rows, n_rows)
-        dev = mask.device
-        with torch.cuda.device(dev):
-            rc = _lib.lib().mgx_action_mask(C.byref(self.sc), n, C.byref(s), _ptr(idx), flags, mask.data_ptr(), _ptr(bad), _stream(dev))
-        _lib.check(rc, "mgx_action_mask")
+        self._row_query("mgx_action_mask", mask.device, n, rows, n_rows, idx, (flags, mask.data_ptr()), bad)
 
     # ------------------------------------------------------------------------------------------ distance fields
     def distance(self, n, rows, n_rows, idx, query, field, agent_dist, bad):
@@ -619,15 +615,11 @@ class HipBackend(KeyTableOps):
         holding `n_rows` rows: cells, agents; idx: i64[n] on the device, None = the identity, read by the kernel as it is) to the
         sources of `query` = {type_mask, colour_mask, agent_mask, flags, points (i16[n,P,2] or None)}, into field i16[n,H,W] and / or
         agent_dist i16[n,A] (one of them may be None).  `bad` i32[2] or None."""
-        s = self._env_rows(rows, n_rows)
         pts = query.get("points")
         q = _lib.MgxDistanceC(query["type_mask"], query["colour_mask"], query["agent_mask"], query["flags"], _ptr(pts),
                               0 if pts is None else int(pts.shape[1]))
         dev = (field if field is not None else agent_dist).device
-        with torch.cuda.device(dev):
-            rc = _lib.lib().mgx_distance(C.byref(self.sc), n, C.byref(s), _ptr(idx), C.byref(q), _ptr(field), _ptr(agent_dist), _ptr(bad),
-                                         _stream(dev))
-        _lib.check(rc, "mgx_distance")
+        self._row_query("mgx_distance", dev, n, rows, n_rows, idx, (C.byref(q), _ptr(field), _ptr(agent_dist)), bad)
 
     def launch_info(self, B) -> dict:
         return _lib.launch_info(self.spec, B)

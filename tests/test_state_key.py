@@ -709,34 +709,18 @@ def test_obs_key_of_the_envs_outputs_and_of_a_rollouts():
 # ---- the C ABI without a GPU -------------------------------------------------------------------------------------------------------
 
 def test_c_abi_argument_validation():
+    """what mgx_state_key and mgx_obs_key check of their own; the checks of every row query: tests/test_row_query_abi.py"""
+    from tests.test_row_query_abi import INV, UNS, P as p, full, ref
     L = _lib.lib()
-    INV, UNS = _lib.ERR_INVALID_ARGUMENT, _lib.ERR_UNSUPPORTED
-    p = 4096                                              # (never dereferenced: every call returns before a launch)
     sc = EnvSpec(5, 5, 2, 3, max_steps=4).to_c()
-    members = [n for n, _ in _lib.MgxEnvRows._fields_[:-1]]
-    full = lambda rows=8, **kw: _lib.MgxEnvRows(*[kw.get(n, p) for n in members], rows)
-    ref = lambda x: C.byref(x) if x is not None else None
 
     def K(sc_, n, src, idx=p, flags=3, salt=2 ** 64 - 1, keys=p, bad=p):
         return L.mgx_state_key(ref(sc_), n, ref(src), idx, flags, salt, keys, bad, None)
     a = full()
-    assert K(None, 4, a) == INV and K(sc, -1, a) == INV and K(sc, 4, None) == INV and K(sc, 4, full(rows=-1)) == INV
     for flags in (4, 8, 0x80000000):
         assert K(sc, 4, a, flags=flags) == INV and K(sc, 0, a, flags=flags) == INV
-    bad = EnvSpec(5, 5, 2, 3).to_c()
-    bad.num_agents = 33
-    assert K(bad, 0, a) == INV
-    bad = EnvSpec(5, 5, 2, 3).to_c()
-    bad.cell_bytes = 4
-    assert K(bad, 4, a) == INV
-    assert K(sc, 0, _lib.MgxEnvRows(), None, 0, 0, None, None) == 0 and K(sc, 0, a) == 0
-    for m in ("cells", "agents", "rng", "step_count"):
-        assert K(sc, 4, full(**{m: None})) == INV, m
     assert K(sc, 4, a, keys=None) == INV
-    for m, off in (("rng", 8), ("aux", 8), ("agents", 4), ("step_count", 2), ("cells", 1)):
-        assert K(sc, 4, full(**{m: p + off})) == INV, m
-    assert K(sc, 4, a, idx=p + 4) == INV and K(sc, 4, a, keys=p + 4) == INV and K(sc, 4, a, bad=p + 2) == INV
-    assert K(sc, 256 * (2 ** 31 - 1) + 1, a) == UNS
+    assert K(sc, 4, a, keys=p + 4) == INV
     big = EnvSpec(5, 5, 2, 3).to_c()
     big.width, big.height = 1024, 129
     assert K(big, 4, a) == UNS
