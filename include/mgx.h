@@ -1016,6 +1016,41 @@ int mgx_key_insert(const MgxKeyTable *table, int64_t n, const int64_t *keys, uin
                    int64_t *first, int32_t *visits, void *stream);
 int mgx_key_lookup(const MgxKeyTable *table, int64_t n, const int64_t *keys, int64_t *entry, int32_t *visits, void *stream);
 
+/* SELECTION (additive to ABI 11): the k best of n, as a list of fixed length, with the count kept on the device -- the beam cut of a
+ * search level, and with no scores a fixed-shape `nonzero`.  In O(n): a radix select for the threshold, then an order-preserving
+ * compaction.  No host work, no synchronisation, capturable in a graph.  Build-defined: the reference has no such notion.
+ *
+ * mgx_select(n, score i32[n] nullable, keep u8[n] nullable, values i64[n] nullable, k, fill, index i64[k], count i32[2], work,
+ * work_bytes, stream).  THE RULE:
+ *   candidates  C = { i < n : keep == NULL or keep[i] != 0 } -- any non-zero byte counts
+ *   m           min(k, |C|)
+ *   chosen      the m candidates smallest by the pair (score[i], i); scores compare as signed int32; with score == NULL the order is
+ *               by i alone.  The chosen set is that of a stable argsort of the candidates' scores, cut at m.
+ *   index       index[0..m) holds the chosen i in ASCENDING i (an order-preserving compaction: with score == NULL the call is a
+ *               `nonzero` of fixed shape); with `values` given, values[i] is written in place of i.  index[m..k) = fill.  No byte
+ *               outside index[0..k) is written.
+ *   count       count[0] = m, count[1] = |C|: the caller sees a cut as count[1] > count[0].  Both words are written by every call,
+ *               never accumulated.
+ * The outputs are a pure function of the inputs, byte-identical from run to run.
+ *
+ * WORK belongs to the caller: at least mgx_select_work_bytes(n) bytes (monotone in n), 16-byte aligned.  Its contents on entry are
+ * arbitrary; the call initialises what it needs with launches of its own on `stream`, so a captured call replays correctly on new data
+ * in the same arrays.  One work buffer takes one call at a time.
+ *
+ * LAUNCHES: six with scores, two without, one for n == 0 -- a function of the arguments, never of the data.
+ *
+ * Return codes, in this order: n < 0, k < 1, score and keep both NULL, NULL index or count: MGX_ERR_INVALID_ARGUMENT; then n == 0:
+ * MGX_OK -- index is all `fill`, count is {0, 0}, one small launch writes them; then NULL or too small `work`, or a misaligned
+ * pointer -- 8 bytes for values and index, 4 for score and count, 16 for work -- MGX_ERR_INVALID_ARGUMENT; then n or k above INT_MAX:
+ * MGX_ERR_UNSUPPORTED.
+ *
+ * LEFT OUT ON PURPOSE: output in rank order (a flag can add it later); float scores; a device-side open list (push / pop-best) built
+ * on this call; a "skip" sentinel for the row indices of mgx_env_copy and the row queries -- that would change a published contract,
+ * so callers pad with a valid row.  csrc/mgx_select.h states the rule for both compilers. */
+size_t mgx_select_work_bytes(int64_t n);
+int mgx_select(int64_t n, const int32_t *score, const uint8_t *keep, const int64_t *values, int64_t k, int64_t fill, int64_t *index,
+               int32_t *count, void *work, size_t work_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

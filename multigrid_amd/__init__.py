@@ -8,9 +8,10 @@ from .constants import Action, Color, Direction, State, Type  # noqa: F401
 from .spec import EnvSpec  # noqa: F401
 from .batched import BatchedMultiGridEnv, EnvSnapshot  # noqa: F401
 from .key_table import KeyInsert, KeyLookup, KeyTable  # noqa: F401
+from .select import Selection, Selector  # noqa: F401
 
 __all__ = ["Action", "Color", "Direction", "State", "Type", "EnvSpec", "BatchedMultiGridEnv", "EnvSnapshot", "KeyTable", "KeyInsert",
-           "KeyLookup"]
+           "KeyLookup", "Selector", "Selection"]
 from .env import Agent, MultiGridEnv  # noqa: F401,E402
 from .envs import (CONFIGURATIONS, BlockedUnlockPickupEnv, EmptyEnv, LockedHallwayEnv, PlaygroundEnv,  # noqa: F401,E402
                    RedBlueDoorsEnv, make, spec_for)

@@ -30,7 +30,7 @@ EXPORTS = ("mgx_abi_version", "mgx_error_string", "mgx_last_hip_error", "mgx_gen
            "mgx_persistent_waves", "mgx_step_persistent", "mgx_persistent_post", "mgx_persistent_wait", "mgx_persistent_feed",
            "mgx_rollout_info", "mgx_render_atlas", "mgx_render", "mgx_reset_select", "mgx_reset_generate_select",
            "mgx_episode_stats", "mgx_episode_restart", "mgx_env_copy", "mgx_state_key", "mgx_obs_key", "mgx_action_mask",
-           "mgx_distance", "mgx_key_insert", "mgx_key_lookup")
+           "mgx_distance", "mgx_key_insert", "mgx_key_lookup", "mgx_select_work_bytes", "mgx_select")
 
 
 class MgxLaunchInfo(C.Structure):
@@ -257,6 +257,12 @@ def lib() -> C.CDLL:
         L.mgx_key_insert.argtypes = [C.POINTER(MgxKeyTableC), i64, vp, C.c_uint32, vp, vp, vp, vp, vp]
         L.mgx_key_lookup.restype = C.c_int
         L.mgx_key_lookup.argtypes = [C.POINTER(MgxKeyTableC), i64, vp, vp, vp, vp]
+    # (... or the selection: only Selector needs it)
+    if is_product_lib() or hasattr(L, "mgx_select"):
+        L.mgx_select_work_bytes.restype = C.c_size_t
+        L.mgx_select_work_bytes.argtypes = [i64]
+        L.mgx_select.restype = C.c_int
+        L.mgx_select.argtypes = [i64, vp, vp, vp, i64, i64, vp, vp, vp, C.c_size_t, vp]
     if L.mgx_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH}: ABI version {L.mgx_abi_version()} != {ABI_VERSION}; rebuild it")
     _lib = L

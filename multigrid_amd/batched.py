@@ -1500,6 +1500,13 @@ class BatchedMultiGridEnv:
         from .key_table import KeyTable
         return KeyTable(capacity, self._cells.device, backend=self.backend)
 
+    def selector(self, n_max: int | None = None):
+        """A `multigrid_amd.Selector` for up to `n_max` items (None: `batch`) on the env's device, launched through the env's
+        backend: the k best of a level by (score, index) as a list of fixed length with the count on the device, and with no scores
+        a fixed-shape `nonzero` (include/mgx.h "SELECTION").  It belongs to the caller, not to the env."""
+        from .select import Selector
+        return Selector(self.batch if n_max is None else n_max, self._cells.device, backend=self.backend)
+
     # ------------------------------------------------------------------------------------------ action masks
     def action_mask(self, env_ids: torch.Tensor | None = None, *, expand: bool = False, out: torch.Tensor | None = None) -> torch.Tensor:
         """Which actions of every agent of the envs `env_ids` can do anything in the state they are in (include/mgx.h "ACTION

@@ -33,7 +33,8 @@ UNITS = ([("mgx_kernels", os.path.join(CSRC, "mgx_kernels.hip"), ()), ("mgx_aux"
           ("mgx_state_key", os.path.join(CSRC, "mgx_state_key.hip"), ()),
           ("mgx_action_mask", os.path.join(CSRC, "mgx_action_mask.hip"), ()),
           ("mgx_distance", os.path.join(CSRC, "mgx_distance.hip"), ()),
-          ("mgx_key_table", os.path.join(CSRC, "mgx_key_table.hip"), ())]
+          ("mgx_key_table", os.path.join(CSRC, "mgx_key_table.hip"), ()),
+          ("mgx_select", os.path.join(CSRC, "mgx_select.hip"), ())]
          + [(f"mgx_fused_v{v}", os.path.join(CSRC, "mgx_fused_inst.hip"), (f"MGX_INST_V={v}",)) for v in VIEWS])
 SRCS = sorted({u[1] for u in UNITS})
 #: everything the library is compiled from: the units, every header and .inc beside them (listed, not named by hand: a header

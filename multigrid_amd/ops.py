@@ -119,6 +119,34 @@ def _load_compiled_ops():
 _load_compiled_ops()
 
 
+class SelectOps:
+    """The launcher of the device selection (include/mgx.h "SELECTION").  It needs no env spec: `multigrid_amd.Selector` makes one of
+    these for a selector that belongs to no env; HipBackend inherits it for `BatchedMultiGridEnv.selector()`."""
+
+    name = "hip"
+
+    def __init__(self, device):
+        KeyTableOps.__init__(self, device)
+
+    @staticmethod
+    def select_work_bytes(n: int) -> int:
+        """mgx_select_work_bytes: the bytes of work buffer a select over n items needs (monotone in n)"""
+        return int(_lib.lib().mgx_select_work_bytes(n))
+
+    def select(self, n, score, keep, values, k, fill, index, count, work):
+        """mgx_select on torch's current stream (six launches with scores, two without): score i32[n], keep u8 / bool [n], values
+        i64[n], each or None (not score and keep both); index i64[k], count i32[2]; `work` a uint8 tensor of select_work_bytes(n)."""
+        dev = index.device
+        if n == 0:
+            # (torch gives an empty tensor the address 0, which the entry point reads as "not given": an empty input stands in with
+            # the work buffer's address -- nothing is read from an input of no items)
+            score, keep, values = (work if t is not None else None for t in (score, keep, values))
+        with torch.cuda.device(dev):
+            rc = _lib.lib().mgx_select(n, _ptr(score), _ptr(keep), _ptr(values), k, fill, index.data_ptr(), count.data_ptr(),
+                                       work.data_ptr(), work.numel() * work.element_size(), _stream(dev))
+        _lib.check(rc, "mgx_select")
+
+
 class KeyTableOps:
     """The launchers of the device key tables (include/mgx.h "KEY TABLES").  They need no env spec: `multigrid_amd.KeyTable` makes
     one of these for a table that belongs to no env; HipBackend inherits them for `BatchedMultiGridEnv.key_table()`."""
@@ -160,7 +188,7 @@ class KeyTableOps:
         _lib.check(rc, "mgx_key_lookup")
 
 
-class HipBackend(KeyTableOps):
+class HipBackend(KeyTableOps, SelectOps):
     """Pre-bound launcher: the state and output tensors of one BatchedMultiGridEnv, validated once."""
 
     name = "hip"
