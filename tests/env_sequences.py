@@ -8,17 +8,29 @@ tests/test_env_sequences_gpu.py (HIP against the oracle).  No tests in here.
   * `compare(a, b, ...)` holds two envs to each other byte for byte; `invariants(env)` are the layout marker's two rules;
     `SeqOracle` is the CPU model of every launcher -- CopyOracle(StatsOracle(SelectOracle(OracleBackend))) -- with a one-hot gen_obs,
     an accounting of its own fed from what the launches hand back (`shadow`: what EpisodeStats must hold whatever the host logic
-    called), and the census of what a run went through."""
+    called), and the census of what a run went through.
+  * the query layer (`make_ops(..., queries=True)`): after every call of the list zero to two READ-ONLY calls -- state_key, obs_key,
+    action_mask, distance_field / agent_distance, the same on a kept snapshot, a key table fed from state keys, a selection over the
+    batch, and (GPU) all of them captured into one graph -- whose arguments come from a generator of their own: the list without
+    them is the list there was before (`without_queries`).  Their launchers on the oracle are the models of the queries' own test
+    files (KeyOracle, MaskOracle, DistOracle, KeyTableModel, SelectModel); what is under test is the host logic in front of the
+    launch: `_copy_entry`, `_row_set`, the snapshot's `_row_set`, `join()`."""
 import weakref
 
 import numpy as np
 import torch
 
 from multigrid_amd import BatchedMultiGridEnv, EnvSpec, _lib, layouts
+from multigrid_amd.key_table import KeyInsert
+from multigrid_amd.select import Selection
 from oracle import binding as ob
 from tests import util
-from tests.test_env_snapshot import TRIO, CopyOracle
+from tests.test_distance import DistOracle
+from tests.test_env_snapshot import TRIO
 from tests.test_episode_stats import model_restart, model_stats, new_state
+from tests.test_key_table import KeyTableModel
+from tests.test_select import SelectModel, threshold
+from tests.test_state_key import SALTS, KeyOracle
 
 NONE, BEFORE, AFTER = _lib.RESTART_NONE, _lib.RESTART_BEFORE, _lib.RESTART_AFTER
 STATE = ("_cells", "agents", "rng", "step_count")
@@ -52,6 +64,9 @@ FIRST_ENV = {"pool4_objects": 11, "gen_between": 11, "bup_candidates": 11}
 #: the pool sizes a form alternates between when `pool_replace` gives it another K
 POOL_K = {"pool1": (1, 2), "pool4_objects": (4, 3), "pool_compact": (2, 3), "big_empty1": (1, 2), "big_objects1": (1, 2),
           "pool1_jit": (1, 2)}
+#: the commonest object type of a form's grids, what `q_select` scores by: the goal of the Empty layouts, a door where the grids are
+#: util.random_state's (three of its ten kinds of cell) and in BlockedUnlockPickup
+COMMON_TYPE = {f: (4 if f in ("plain", "plain_jit", "pool4_objects", "big_objects1", "bup_candidates") else 8) for f in SPECS}
 #: (type, color, state) triples a cell edit writes: every cell format holds them, and an agent may stand on each (the edit may land
 #: under one): empty, floors, lava, a goal
 EDIT_CELLS = np.array([[1, 0, 0], [3, 3, 0], [3, 1, 0], [9, 0, 0], [8, 1, 0], [3, 4, 0]], np.uint8)
@@ -63,7 +78,29 @@ GPU_KINDS = ("capture_replay", "graph_again", "persistent", "step_chains")
 #: what a recorded stretch may hold: functions of the env state and the call's arguments (the time machine); `one_hot_obs` is a
 #: function of the `obs` buffer, which is no part of a snapshot
 PURE_KINDS = ("step", "step_one_hot", "rollout", "reset_done", "reset", "snapshot", "snapshot_out", "restore", "fork", "edit", "seed",
-              "gen_obs", "full_obs", "capture_replay", "step_chains")
+              "gen_obs", "full_obs", "capture_replay", "step_chains", "q_state_key", "q_action_mask", "q_distance", "q_snap", "q_select")
+#: the query layer: calls that write nothing.  ROW_QUERIES go through `_row_set` of the env (q_table and q_select begin with one), so
+#: each of them may be the first consumer of pending sub-shard chains; `q_obs_key` reads the `obs` buffer and `q_table` a table of
+#: its own: not pure
+ROW_QUERIES = ("q_state_key", "q_action_mask", "q_distance")
+QUERY_KINDS = ROW_QUERIES + ("q_obs_key", "q_snap", "q_table", "q_select", "q_graph", "q_graph_again")
+FIRST_CONSUMERS = ROW_QUERIES + ("q_table", "q_select")
+GPU_QUERY_KINDS = ("q_graph", "q_graph_again")
+QUERY_WEIGHTS = {"q_state_key": 3, "q_obs_key": 1.5, "q_action_mask": 3, "q_distance": 4, "q_snap": 3.5, "q_table": 4, "q_select": 1.5,
+                 "q_graph": 1, "q_graph_again": 1.5}
+#: how many queries follow a call
+QUERY_COUNT_P = (0.3, 0.4, 0.3)
+#: rows per query.  The oracle's query models walk their rows in Python: at 40 rows, a whole batch every eighth query and a
+#: selection as often as a row query the GPU cases took 2.5 to 3 times their time without the layer (profiles/env_sequences_queries.txt);
+#: the rows were cut, not the queries
+MAX_QUERY_ROWS = 24
+#: the object types a distance query may name (goal, key, ball, box, door, lava), and per form the commonest one: what `q_select` scores by
+SOURCE_TYPES = (8, 5, 6, 7, 4, 9)
+THROUGH = ("closed", "locked", "objects")
+TABLE_CAPACITY = 1 << 12
+#: `q_select` at the batch that reads the marker: one pass over the first envs only
+SELECT_MAX = 4096
+MAX_QUERY_GRAPHS = 3
 #: relative frequencies; every legal kind must run at least three times over a form's seeds (the census of the tests)
 WEIGHTS = {"step": 8, "step_one_hot": 2, "rollout": 3, "reset_done": 2, "reset": 3, "snapshot": 4, "snapshot_out": 2, "restore": 5,
            "fork": 2, "edit": 3, "load_state_dict": 1.6, "pool_refill": 1.6, "pool_replace": 1.4, "track": 3.0, "reset_totals": 2.6,
@@ -73,8 +110,9 @@ WEIGHTS = {"step": 8, "step_one_hot": 2, "rollout": 3, "reset_done": 2, "reset":
 
 # ---- the oracle launcher ------------------------------------------------------------------------------------------------------------
 
-class SeqOracle(CopyOracle):
-    """The CPU model of every launcher, and what watches a run:
+class SeqOracle(KeyOracle, DistOracle, KeyTableModel, SelectModel):
+    """The CPU model of every launcher -- the queries' launchers are the models of their own test files, composed: KeyOracle and
+    DistOracle (which is MaskOracle too) over the one CopyOracle, the key table's and the selection's mixins --, and what watches a run:
 
     shadow   the accounting's tensors as they must be, or None while it is off: updated HERE from what each stepping / restart launch
              hands back, by the sequential model -- not by the accounting calls the host logic makes, which it checks.  A restore
@@ -282,21 +320,40 @@ def legal_kinds(form, B, gpu):
     return kinds
 
 
-def make_ops(form, B, n_ops, seed, gpu=False, stretch=None, weights=None, kinds=None, every_third=None):
+def legal_query_kinds(form, B, gpu):
+    """every query kind `form` can meet at batch B: `_copy_entry` admits a query wherever the list stands between two calls (no session
+    is open there, a state is loaded, the env is no sub-shard)"""
+    return list(QUERY_KINDS[:-2]) + (list(GPU_QUERY_KINDS) if gpu else [])
+
+
+def without_queries(ops):
+    return [o for o in ops if o["kind"] not in QUERY_KINDS]
+
+
+def make_ops(form, B, n_ops, seed, gpu=False, stretch=None, weights=None, kinds=None, every_third=None, queries=False):
     """The whole list of calls of one sequence.
 
     gpu          the GPU-only kinds are in
     stretch      (s, e): call s is `tm_begin` (a snapshot of the whole batch, the kept ones forgotten), and the calls s+1 .. e-1 are
                  PURE_KINDS that use only snapshots taken after s -- what the time machine records, restores and repeats
-    kinds        restrict the kinds drawn (the large-batch test); every_third: that call at every third index instead of a draw"""
+    kinds        restrict the kinds drawn (the large-batch test); every_third: that call at every third index instead of a draw
+    queries      the query layer: zero to two QUERY_KINDS behind every call, drawn from a generator of their own (`rq`), so that
+                 `without_queries()` of the list is the list of queries=False, arguments included; n_ops, `stretch` and every_third
+                 count the other calls.  A `step_chains` directly in front of a query that goes through the env's `_row_set` is
+                 not joined by apply(): the query carries first_consumer=True, and its own join() is what orders it behind the
+                 chains."""
     r = np.random.default_rng([seed, B, (FORMS + BIG_FORMS + JIT_FORMS).index(form)])
+    rq = np.random.default_rng([seed, B, (FORMS + BIG_FORMS + JIT_FORMS).index(form), 1])
     spec = SPECS[form]
     A, H, W = spec.num_agents, spec.height, spec.width
     source = form not in PLAIN_FORMS
-    w = dict(WEIGHTS, **(weights or {}))
-    allowed = set(legal_kinds(form, B, gpu)) if kinds is None else set(kinds)
+    w = dict(WEIGHTS, **QUERY_WEIGHTS)
+    w.update(weights or {})
+    allowed = set(legal_kinds(form, B, gpu) + legal_query_kinds(form, B, gpu)) if kinds is None else set(kinds)
     S = {"tracking": None, "snaps": {}, "graphs": {}, "version": 0, "persistent": 0, "K": POOL_K.get(form, (0,))[0], "next_slot": 0,
-         "next_graph": 0, "staged": form in ("gen_candidates", "gen_between", "bup_candidates")}
+         "next_graph": 0, "staged": form in ("gen_candidates", "gen_between", "bup_candidates"),
+         # (what the query layer keeps, from the calls' arguments alone: no draw of `r` depends on it)
+         "epoch": 0, "touched": np.zeros(B, bool), "qgraphs": {}, "next_qgraph": 0, "last_table_ids": None}
 
     def actions(*lead):
         a = r.integers(0, 7, size=lead + (B, A)).astype(np.int8)
@@ -332,7 +389,7 @@ def make_ops(form, B, n_ops, seed, gpu=False, stretch=None, weights=None, kinds=
             e = None if r.random() < 0.4 else ids(distinct=bool(r.random() < 0.7))
             slot = S["next_slot"]
             S["next_slot"] = (slot + 1) % MAX_SNAPS
-            S["snaps"][slot] = {"rows": B if e is None else len(e), "tracked": tracked, "pure": pure, "all": e is None}
+            S["snaps"][slot] = {"rows": B if e is None else len(e), "tracked": tracked, "pure": pure, "all": e is None, "epoch": S["epoch"]}
             op.update(slot=slot, env_ids=e)
         elif kind == "snapshot_out":
             fit = [s for s in usable(pure) if S["snaps"][s]["tracked"] == tracked]
@@ -341,7 +398,7 @@ def make_ops(form, B, n_ops, seed, gpu=False, stretch=None, weights=None, kinds=
             slot = int(r.choice(fit))
             v = S["snaps"][slot]
             e = None if v["all"] and r.random() < 0.5 else ids(v["rows"])
-            v.update(pure=pure, all=v["all"] and e is None)
+            v.update(pure=pure, all=v["all"] and e is None, epoch=S["epoch"])
             op.update(slot=slot, env_ids=e)
         elif kind == "restore":
             have = usable(pure)
@@ -418,23 +475,138 @@ def make_ops(form, B, n_ops, seed, gpu=False, stretch=None, weights=None, kinds=
             return None
         return op
 
-    ops, ran = [], {}
-    for i in range(n_ops):
-        pure = stretch is not None and stretch[0] < i < stretch[1]
+    # ---- the query layer: every draw below is one of `rq`
+    def q_ids(rows=B):
+        """row indices of a query: 1..MAX_QUERY_ROWS of them, repeated half the time; now and then None (every row, in order)"""
+        if rows <= 160 and rq.random() < 0.05:  # (the whole of a small batch or snapshot; never of the large batch)
+            return None
+        n = int(rq.integers(1, min(rows, MAX_QUERY_ROWS) + 1))
+        return (rq.integers(0, rows, size=n) if rq.random() < 0.5 else rq.permutation(rows)[:n]).astype(np.int64)
+
+    def q_subset(values, lo=1):
+        values = list(values)
+        n = int(rq.integers(lo, len(values) + 1))
+        return sorted(int(v) for v in rq.permutation(values)[:n])
+
+    def q_args(which, n):
+        """the keyword arguments of one row query over n output rows"""
+        if which == "key":
+            return {"salt": SALTS[int(rq.integers(0, 2))], "step_count": bool(rq.random() < 0.5), "rng": bool(rq.random() < 0.5)}
+        if which == "mask":
+            return {"expand": bool(rq.random() < 0.5)}
+        q = {"field": bool(rq.random() < 0.35), "types": None, "colors": None, "agents": None, "points": None,
+             "through": tuple(t for t in THROUGH if rq.random() < 0.5), "avoid_lava": bool(rq.random() < 0.4)}
+        mode = int(rq.integers(0, 6))
+        if mode in (0, 1, 4):
+            q["types"] = q_subset(SOURCE_TYPES)[:3]
+        if mode == 1:
+            q["colors"] = q_subset(range(6))[:3]
+        if mode in (2, 4):
+            q["agents"] = q_subset(range(A))
+        if mode in (3, 5) or rq.random() < 0.15:
+            # (x, y) per output row, some outside the grid; every third row has none inside: a row without a source
+            P = int(rq.integers(1, 4))
+            pts = np.stack([rq.integers(-2, W + 2, size=(n, P)), rq.integers(-2, H + 2, size=(n, P))], axis=-1).astype(np.int16)
+            pts[rq.random(n) < 0.33] = (W + 1, -1)
+            q["points"] = pts
+        return q
+
+    def draw_query(kind, pure, chained):
+        op = {"kind": kind}
+        if kind in ROW_QUERIES:
+            e = q_ids()
+            op.update(ids=e, keep_out=bool(rq.random() < 0.5), **q_args(kind[2:].split("_")[-1], B if e is None else len(e)))
+        elif kind == "q_snap":
+            have = usable(pure)
+            if not have:
+                return None
+            stale = [s for s in have if S["snaps"][s]["epoch"] < S["epoch"]]
+            slot = int(rq.choice(stale if stale and rq.random() < 0.5 else have))
+            v = S["snaps"][slot]
+            e = q_ids(v["rows"])
+            which = ("key", "mask", "distance")[int(rq.integers(0, 3))]
+            op.update(slot=slot, ids=e, which=which, keep_out=bool(rq.random() < 0.5), stale=v["epoch"] < S["epoch"],
+                      **q_args(which, v["rows"] if e is None else len(e)))
+        elif kind == "q_table":
+            e = q_ids()
+            e = np.arange(min(B, MAX_QUERY_ROWS), dtype=np.int64) if e is None else e
+            last = S["last_table_ids"]
+            if last is not None and rq.random() < 0.6:          # (envs the table may know: half of the last call's)
+                e = np.concatenate([last[:(len(last) + 1) // 2], e])[:MAX_QUERY_ROWS] if B > MAX_QUERY_ROWS else e
+            S["last_table_ids"] = e
+            op.update(ids=e, mode="insert" if rq.random() < 0.6 else "lookup", count=bool(rq.random() < 0.5))
+        elif kind == "q_select":
+            op.update(type=COMMON_TYPE[form], k=("one", "less", "all", "more", "pad")[int(rq.integers(0, 5))],
+                      values=bool(rq.random() < 0.5), fill=(-1, 12345)[int(rq.integers(0, 2))], keep_out=bool(rq.random() < 0.5))
+        elif kind == "q_graph":
+            n = int(rq.integers(1, min(B, MAX_QUERY_ROWS) + 1))
+            g = S["next_qgraph"] % MAX_QUERY_GRAPHS
+            S["next_qgraph"] += 1
+            op.update(graph=g, ids=rq.integers(0, B, size=n).astype(np.int64), type=COMMON_TYPE[form], k=int(rq.integers(1, n * A + 3)),
+                      salt=SALTS[int(rq.integers(0, 2))], step_count=bool(rq.random() < 0.5), rng=bool(rq.random() < 0.5),
+                      through=tuple(t for t in THROUGH if rq.random() < 0.5), avoid_lava=bool(rq.random() < 0.4))
+            S["qgraphs"][g] = {"version": S["version"], "op": op}
+        elif kind == "q_graph_again":
+            live = [g for g, v in S["qgraphs"].items() if v["version"] == S["version"]]
+            if not live:
+                return None
+            op = dict(S["qgraphs"][int(rq.choice(live))]["op"], kind="q_graph_again")
+        if kind in ROW_QUERIES:
+            e = op["ids"]
+            op["hits_touched"] = bool(S["touched"].all() if e is None else S["touched"][e].any())
+            S["touched"][...] = False
+        if chained:
+            op["first_consumer"] = True
+        return op
+
+    def draw_queries(prev, pure):
+        """zero to two queries behind `prev`; behind a step_chains at least one, and that one through the env's `_row_set`"""
+        if not queries:
+            return []
+        chained = prev["kind"] == "step_chains"
+        n = max(int(rq.choice(3, p=QUERY_COUNT_P)), 1 if chained else 0)
+        out = []
+        for j in range(n):
+            first = chained and j == 0
+            names = sorted(k for k in allowed if k in QUERY_KINDS and (not pure or k in PURE_KINDS)
+                           and (not first or k in (FIRST_CONSUMERS if not pure else ROW_QUERIES + ("q_select",))))
+            if not names:
+                break
+            p = np.array([w[k] * (4 if qran.get(k, 0) < 2 else 1) for k in names], float)
+            for _ in range(8):                               # (a kind with nothing to work on -- no snapshot, no graph -- gives way)
+                op = draw_query(names[int(rq.choice(len(names), p=p / p.sum()))], pure, first)
+                if op is not None:
+                    qran[op["kind"]] = qran.get(op["kind"], 0) + 1
+                    out.append(op)
+                    break
+        return out
+
+    def note(op):
+        """what the query layer remembers of a call: which envs it restored, reset or edited, and that the pool or the state changed
+        under the kept snapshots (the calls' arguments alone)"""
+        k = op["kind"]
+        if k in ("load_state_dict", "pool_refill", "pool_replace"):
+            S["epoch"] += 1
+        if k == "restore":
+            S["touched"][op["env_ids"] if op["env_ids"] is not None else slice(None)] = True
+        elif k == "reset":
+            S["touched"][op["mask"].astype(bool) if op["mask"] is not None else slice(None)] = True
+        elif k == "edit":
+            S["touched"][op["env_ids"]] = True
+        elif k == "fork":
+            S["touched"][op["dst"]] = True
+
+    def main_op(i, pure):
         if stretch is not None and i == stretch[0]:
             S["snaps"] = {}
-            ops.append({"kind": "tm_begin"})
-            continue
+            return {"kind": "tm_begin"}
         if every_third is not None and i % 3 == 2:
-            ops.append({"kind": "step", "acts": actions(), "auto_reset": True})
-            continue
+            return {"kind": "step", "acts": actions(), "auto_reset": True}
         if every_third is not None and i % 9 == 3:           # (an edit right behind a step whose restarts marked their envs)
-            ops.append(draw("edit", pure))
-            continue
+            return draw("edit", pure)
         if pure and i == stretch[0] + 3:                     # (so that the stretch has a snapshot of its own to restore and fork from)
-            ops.append(draw("snapshot", pure))
-            continue
-        names = sorted(k for k in allowed if not pure or k in PURE_KINDS)
+            return draw("snapshot", pure)
+        names = sorted(k for k in allowed if k not in QUERY_KINDS and (not pure or k in PURE_KINDS))
         # (a kind the list has met less than twice is four times as likely: every list holds every kind its form allows)
         p = np.array([w[k] * (4 if ran.get(k, 0) < 2 else 1) for k in names], float)
         while True:
@@ -442,7 +614,15 @@ def make_ops(form, B, n_ops, seed, gpu=False, stretch=None, weights=None, kinds=
             if op is not None:
                 break
         ran[op["kind"]] = ran.get(op["kind"], 0) + 1
+        return op
+
+    ops, ran, qran = [], {}, {}
+    for i in range(n_ops):
+        pure = stretch is not None and stretch[0] < i < stretch[1]
+        op = main_op(i, pure)
         ops.append(op)
+        note(op)
+        ops.extend(draw_queries(op, pure or op["kind"] == "tm_begin"))     # (behind the snapshot: part of what is repeated)
     return ops
 
 
@@ -460,16 +640,17 @@ def describe(op) -> str:
 # ---- performing a call --------------------------------------------------------------------------------------------------------------
 
 def new_ctx():
-    return {"snaps": {}, "graphs": {}, "tm": None}
+    return {"snaps": {}, "graphs": {}, "tm": None, "outs": {}, "table": None, "selector": None, "qgraphs": {}, "warm_table": None}
 
 
 def is_hip(env) -> bool:
     return getattr(env.backend, "name", "") == "hip"
 
 
-def apply(env, op, ctx) -> dict:
+def apply(env, op, ctx, nxt=None) -> dict:
     """One call on `env`.  Returns what the call wrote or handed back that is not part of the env state: name -> tensor (the env's
-    own output buffers by name, a rollout's dict under 'out.<key>')."""
+    own output buffers by name, a rollout's dict and a query's answers under 'out.<key>').  nxt: the call that follows in the list
+    (`following`), which decides the shape of a step_chains."""
     dev, kind, hip = env.device, op["kind"], is_hip(env)
     be = env.backend
 
@@ -596,9 +777,176 @@ def apply(env, op, ctx) -> dict:
         if not hip:
             return steps(op["acts"][None], op["auto_reset"])
         env.step(dv(op["acts"]), auto_reset=op["auto_reset"], sub_shards=2)
+        if unjoined(op, nxt):                                  # (the query that follows joins: nothing may read this env before it)
+            return {}
         env.join()
         return outputs(op["auto_reset"])
+    if kind in QUERY_KINDS:
+        outs = apply_query(env, op, ctx)
+        if op.get("first_consumer"):                           # (behind the query's join(): what the unjoined step handed back)
+            outs.update({n: getattr(env, n) for n in OUTPUTS})
+        return outs
     raise ValueError(f"unknown call kind {kind!r}")
+
+
+def unjoined(op, nxt) -> bool:
+    """`op` is a step_chains whose join() is left to the query `nxt` that follows it (on the HIP env: nothing may read the env in between)"""
+    return op["kind"] == "step_chains" and nxt is not None and bool(nxt.get("first_consumer"))
+
+
+def following(ops, i):
+    return ops[i + 1] if i + 1 < len(ops) else None
+
+
+WHICH = {"q_state_key": "key", "q_action_mask": "mask", "q_distance": "distance"}
+
+
+def apply_query(env, op, ctx) -> dict:
+    """One call of the query layer on `env`: what it answered, under 'out.<name>' keys.  On an oracle-backed env the answers also feed
+    the census (what a query met can only be seen in its answer)."""
+    dev, kind = env.device, op["kind"]
+    be, sp = env.backend, env.spec
+    A, H, W = sp.num_agents, sp.height, sp.width
+    seen = be._count if isinstance(be, SeqOracle) else (lambda what, n=1: None)
+
+    def dv(a):
+        return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+    def kept(name, shape, dtype, fill):
+        """the tensor this context keeps for out= of that name and shape"""
+        key = (name,) + tuple(shape)
+        if key not in ctx["outs"]:
+            ctx["outs"][key] = torch.full(tuple(shape), fill, dtype=dtype, device=dev)
+        return ctx["outs"][key]
+
+    def row_query(target, which, a, n_rows):
+        idx = dv(a["ids"])
+        n = n_rows if idx is None else int(idx.shape[0])
+        keep = a.get("keep_out", False)
+        if which == "key":
+            out = kept("key", (n,), torch.int64, 0) if keep else None
+            return target.state_key(idx, salt=a["salt"], step_count=a["step_count"], rng=a["rng"], out=out)
+        if which == "mask":
+            shape, dt = ((n, A, 7), torch.bool) if a["expand"] else ((n, A), torch.uint8)
+            res = target.action_mask(idx, expand=a["expand"], out=kept("mask", shape, dt, 0) if keep else None)
+            if isinstance(be, SeqOracle):
+                bits = res[..., 2:6] if a["expand"] else ((res[..., None].to(torch.int32) >> torch.arange(2, 6)) & 1).bool()
+                seen("mask_with_a_clear_and_a_set_bit_beyond_the_turns", int(bool(bits.any()) and not bool(bits.all())))
+            return res
+        field = a["field"]
+        out = kept("dist", (n, H, W) if field else (n, A), torch.int16, -1) if keep else None
+        res = (target.distance_field if field else target.agent_distance)(
+            idx, types=a["types"], colors=a["colors"], agents=a["agents"], points=dv(a["points"]), through=a["through"],
+            avoid_lava=a["avoid_lava"], out=out)
+        if isinstance(be, SeqOracle) and not field and bool((res < 0).any()) and bool((res >= 0).any()):
+            seen("agent_distance_with_and_without_a_way")
+        return res
+
+    def table():
+        if ctx.get("table") is None:
+            ctx["table"] = env.key_table(TABLE_CAPACITY)
+        return ctx["table"]
+
+    def selector():
+        if ctx.get("selector") is None:
+            ctx["selector"] = env.selector(max(min(env.batch, SELECT_MAX), MAX_QUERY_ROWS * A))
+        return ctx["selector"]
+
+    if kind in ROW_QUERIES:
+        return {"out." + WHICH[kind]: row_query(env, WHICH[kind], op, env.batch)}
+    if kind == "q_obs_key":
+        return {"out.obs_key": env.obs_key()}
+    if kind == "q_snap":
+        snap = ctx["snaps"][op["slot"]]
+        return {"out.snap_" + op["which"]: row_query(snap, op["which"], op, snap.rows)}
+    if kind == "q_table":
+        keys = env.state_key(dv(op["ids"]))
+        t = table()
+        if op["mode"] == "insert":
+            res = t.insert(keys, first=True, visits=True, count=op["count"])
+            outs = {"out.is_new": res.is_new, "out.first": res.first, "out.visits": res.visits}
+            if isinstance(be, SeqOracle):
+                known = ~res.is_new & (res.first == torch.arange(keys.numel()))       # (the first holder of a key the table had)
+                if bool(res.is_new.any()) and bool(known.any()):
+                    seen("insert_of_new_and_known_keys")
+        else:
+            res = t.lookup(keys, visits=True)
+            outs = {"out.held": res.entry >= 0, "out.visits": res.visits}
+            seen("lookup_with_a_miss", int(isinstance(be, SeqOracle) and bool((res.entry < 0).any())))
+        # (what include/mgx.h promises whatever the placement: not the entry ids)
+        outs["out.entries"] = torch.tensor([t.entries(), t.dropped()], dtype=torch.int64)
+        return outs
+    if kind == "q_select":
+        n = min(env.batch, SELECT_MAX)
+        ids = None if n == env.batch else torch.arange(n, device=dev)
+        dist = env.agent_distance(ids, types=[op["type"]])        # (first: its join() is what may order the rest behind the chains)
+        score = dist[:, 0].to(torch.int32).contiguous()
+        keep = env.agents[:n, 0, 4] == 0
+        cand = int(keep.sum())
+        k = max(1, {"one": 1, "less": cand - 1, "all": cand, "more": cand + 1, "pad": env.batch + 9}[op["k"]])
+        values = torch.arange(n, device=dev) * 3 + 1 if op["values"] else None
+        out = Selection(kept("index", (k,), torch.int64, 0), kept("count", (2,), torch.int32, 0)) if op["keep_out"] else None
+        res = selector().select(score, keep, k=k, values=values, fill=op["fill"], out=out)
+        if isinstance(be, SeqOracle) and cand:
+            if k < cand:
+                T, quota, tied, _ = threshold(score.numpy(), keep.numpy(), k)
+                seen("select_cut_inside_a_tie", int(tied > quota))
+            seen("select_padded", int(k > cand))
+        return {"out.index": res.index, "out.count": res.count, "out.score": score}
+    if kind in GPU_QUERY_KINDS:
+        return query_graph(env, op, ctx, table(), selector())
+    raise ValueError(f"unknown query kind {kind!r}")
+
+
+def query_graph(env, op, ctx, table, selector) -> dict:
+    """q_graph: state_key + action_mask + agent_distance + table.insert(count=False) + select of one set of rows, captured into one
+    torch.cuda.graph and replayed once (the graph is kept in its slot); q_graph_again: that graph replayed.  The oracle-backed env
+    makes the same calls eagerly, both times."""
+    dev, A = env.device, env.spec.num_agents
+    idx = torch.from_numpy(op["ids"]).to(dev)
+    n = int(idx.shape[0])
+
+    def buffers():
+        return {"keys": torch.zeros(n, dtype=torch.int64, device=dev), "mask": torch.zeros((n, A), dtype=torch.uint8, device=dev),
+                "dist": torch.full((n, A), -1, dtype=torch.int16, device=dev), "score": torch.zeros((n, A), dtype=torch.int32, device=dev),
+                "insert": KeyInsert(torch.zeros(n, dtype=torch.int64, device=dev), torch.zeros(n, dtype=torch.bool, device=dev), None, None),
+                "select": Selection(torch.zeros(op["k"], dtype=torch.int64, device=dev), torch.zeros(2, dtype=torch.int32, device=dev))}
+
+    def calls(b, t):
+        env.state_key(idx, salt=op["salt"], step_count=op["step_count"], rng=op["rng"], out=b["keys"])
+        env.action_mask(idx, out=b["mask"])
+        env.agent_distance(idx, types=[op["type"]], through=op["through"], avoid_lava=op["avoid_lava"], out=b["dist"])
+        b["score"].copy_(b["dist"])
+        t.insert(b["keys"], count=False, out=b["insert"])
+        selector.select(b["score"], k=op["k"], out=b["select"])
+
+    def answers(b):
+        return {"out.g_keys": b["keys"], "out.g_mask": b["mask"], "out.g_dist": b["dist"], "out.g_is_new": b["insert"].is_new,
+                "out.g_index": b["select"].index, "out.g_count": b["select"].count}
+
+    if not is_hip(env):
+        b = buffers()
+        calls(b, table)
+        return answers(b)
+    if op["kind"] == "q_graph_again":
+        graph, b, _ = ctx["qgraphs"][op["graph"]]
+        graph.replay()
+        return answers(b)
+    # everything bound and allocated before the capture, by one eager pass -- into a table of its own: the insert is no query
+    if ctx.get("warm_table") is None:
+        ctx["warm_table"] = env.key_table(64)
+    ctx["warm_table"].clear()
+    b = buffers()
+    cur, side, graph = torch.cuda.current_stream(dev), torch.cuda.Stream(dev), torch.cuda.CUDAGraph()
+    side.wait_stream(cur)
+    with torch.cuda.stream(side):
+        calls(buffers(), ctx["warm_table"])
+        with torch.cuda.graph(graph, stream=side):
+            calls(b, table)
+    cur.wait_stream(side)
+    graph.replay()
+    ctx["qgraphs"][op["graph"]] = (graph, b, idx)
+    return answers(b)
 
 
 # ---- looking at an env --------------------------------------------------------------------------------------------------------------
@@ -713,6 +1061,12 @@ def census_of(ops_lists, oracles) -> dict:
             c[op["kind"]] = c.get(op["kind"], 0) + 1
             if op["kind"] == "restore" and op["repeated"]:
                 c["restore_with_repeated_rows"] = c.get("restore_with_repeated_rows", 0) + 1
+        for j, op in enumerate(ops):                          # (the query layer's conditions that a list shows by itself)
+            for flag, what in (("hits_touched", "row_query_of_an_env_restored_reset_or_edited_since_the_last"),
+                               ("stale", "snapshot_query_older_than_a_pool_or_state_change"),
+                               ("first_consumer", "query_as_first_consumer_of_the_chains")):
+                if op.get(flag):
+                    c[what] = c.get(what, 0) + 1
         seq = [op["value"] is not None for op in ops if op["kind"] == "track"]
         runs = [v for j, v in enumerate(seq) if j == 0 or v != seq[j - 1]]
         if runs[:3] == [True, False, True] or runs[:4] == [False, True, False, True]:
@@ -723,9 +1077,13 @@ def census_of(ops_lists, oracles) -> dict:
     return c
 
 
-def assert_census(c, form, B, gpu=False):
+def assert_census(c, form, B, gpu=False, queries=False):
     """Every legal kind at least three times (a GPU-only kind: at least once); the restarts, restores and switches that the
-    cross-feature rules are about at least once."""
+    cross-feature rules are about at least once.  queries: the same for the query kinds, and what the query layer is there to meet
+    -- a row query of an env just restored, reset or edited; a snapshot queried after the pool or the state changed under it; an
+    insert of new and known keys, a lookup that misses; a selection cut inside a tie and one padded; distances with and without a
+    way in one answer; a mask with a clear and a set bit beyond the turns; with the chains, two queries that are their first
+    consumer."""
     for k in legal_kinds(form, B, gpu):
         need = 1 if k in GPU_KINDS else 3
         assert c.get(k, 0) >= need, f"form {form}: call kind {k} ran {c.get(k, 0)} time(s), {need} needed: {c}"
@@ -736,6 +1094,18 @@ def assert_census(c, form, B, gpu=False):
             need.append("restart_by_termination")
     for k in need:
         assert c.get(k, 0) >= 1, f"form {form}: {k} never happened: {c}"
+    if not queries:
+        return
+    for k in legal_query_kinds(form, B, gpu):
+        need_k = 1 if k in GPU_QUERY_KINDS else 3
+        assert c.get(k, 0) >= need_k, f"form {form}: query kind {k} ran {c.get(k, 0)} time(s), {need_k} needed: {c}"
+    need = {"row_query_of_an_env_restored_reset_or_edited_since_the_last": 1, "snapshot_query_older_than_a_pool_or_state_change": 1,
+            "insert_of_new_and_known_keys": 1, "lookup_with_a_miss": 1, "select_cut_inside_a_tie": 1, "select_padded": 1,
+            "agent_distance_with_and_without_a_way": 1, "mask_with_a_clear_and_a_set_bit_beyond_the_turns": 1}
+    if gpu and B >= 128:
+        need["query_as_first_consumer_of_the_chains"] = 2
+    for k, n in need.items():
+        assert c.get(k, 0) >= n, f"form {form}: {k} happened {c.get(k, 0)} time(s), {n} needed: {c}"
 
 
 # ---- pinned cases: the cross-feature rules, one short list each, in the grammar of make_ops ------------------------------------------
