@@ -14,7 +14,12 @@ tests/test_env_sequences_gpu.py (HIP against the oracle).  No tests in here.
     batch, and (GPU) all of them captured into one graph -- whose arguments come from a generator of their own: the list without
     them is the list there was before (`without_queries`).  Their launchers on the oracle are the models of the queries' own test
     files (KeyOracle, MaskOracle, DistOracle, KeyTableModel, SelectModel); what is under test is the host logic in front of the
-    launch: `_copy_entry`, `_row_set`, the snapshot's `_row_set`, `join()`."""
+    launch: `_copy_entry`, `_row_set`, the snapshot's `_row_set`, `join()`.
+  * the hook forms (HOOK_FORMS): RedBlueDoors, LockedHallway, Playground's generator and the declared rules, whose steps rewrite
+    `aux` -- the 16 hook-state bytes that EnvSnapshot, fork, state_dict, the candidate slots and a pool's `auxs` must carry.  Random
+    walks do not reach hook events, so the starts do: the pool forms restart from hook-dense states of tests/hook_states.py with
+    their aux (`hook_pool`).  The stepping calls of the RedBlueDoors and LockedHallway forms carry a `hook_order`, which sends
+    step() through its slow entry.  The census (`SeqOracle._hook_census`, HOOK_NEED) asks for what these forms are there to meet."""
 import weakref
 
 import numpy as np
@@ -24,6 +29,7 @@ from multigrid_amd import BatchedMultiGridEnv, EnvSpec, _lib, layouts
 from multigrid_amd.key_table import KeyInsert
 from multigrid_amd.select import Selection
 from oracle import binding as ob
+from tests import hook_states as hs
 from tests import util
 from tests.test_distance import DistOracle
 from tests.test_env_snapshot import TRIO
@@ -35,17 +41,38 @@ from tests.test_state_key import SALTS, KeyOracle
 NONE, BEFORE, AFTER = _lib.RESTART_NONE, _lib.RESTART_BEFORE, _lib.RESTART_AFTER
 STATE = ("_cells", "agents", "rng", "step_count")
 OUTPUTS = ("obs", "dir", "reward", "terminated", "truncated")
-FORMS = ("plain", "pool1", "pool4_objects", "pool_compact", "gen", "gen_candidates", "gen_between", "bup_candidates")
+#: the forms of the hook kinds whose step rewrites `aux`, the 16 hook-state bytes (RedBlueDoors, LockedHallway, the declared rules), and
+#: Playground's generator: the generator forms start their episodes on the device (one candidate per env; Playground falls back to
+#: "between"), the pool forms from hook-dense states of tests/hook_states.py -- one or two actions before a success, a failure or an
+#: outcome that depends on the visiting order, as `pool1`'s start is one cell before the goal
+HOOK_FORMS = ("rbd_candidates", "rbd_pool", "lh_candidates", "lh_pool", "playground_between", "rules_pool", "lh12_pool")
+FORMS = ("plain", "pool1", "pool4_objects", "pool_compact", "gen", "gen_candidates", "gen_between", "bup_candidates") + HOOK_FORMS
 #: the batch whose launches READ the layout marker (more than 2048 wavefronts, one layout): tests/test_env_sequences_gpu.py
 BIG_FORMS = ("big_empty1", "big_objects1")
 #: `plain` and `pool1` on shapes of their own -- grids that are not square --, which the HIP env steps on a kernel compiled at run time
 #: (make_env(specialise=True); a registration serves every env of its geometry for the rest of the process: no other form, and no
 #: other test file, uses these shapes): tests/test_jit_forms_gpu.py
 JIT_FORMS = ("plain_jit", "pool1_jit")
+#: a form's place in this list seeds its lists: new forms go to the END (the lists of the others must not change by one argument)
+SEED_ORDER = FORMS[:8] + BIG_FORMS + JIT_FORMS + HOOK_FORMS
 PLAIN_FORMS = ("plain", "plain_jit")                         # no restart source: load_state alone
 POOL1_FORMS = ("pool1", "pool1_jit")
-POOL_FORMS = ("pool1", "pool4_objects", "pool_compact") + BIG_FORMS + ("pool1_jit",)
-GEN_FORMS = ("gen", "gen_candidates", "gen_between", "bup_candidates")
+#: the hook pool forms and the case of tests/hook_states.py whose 512 base states their pools are taken from
+#: (lh_pool: two rooms, the explicit aux -- door positions listed; lh12_pool: twelve rooms and three agents, the geometric aux, whose
+#: unlocked-door mask has a second byte)
+HOOK_CASE = {"rbd_pool": "rbd_a2_all_v7", "lh_pool": "lh2_a2_own_v7", "rules_pool": "rules_fetchtrap_a2_v7", "lh12_pool": "lh12_a3_own_v7"}
+HOOK_POOL_FORMS = tuple(HOOK_CASE)
+POOL_FORMS = ("pool1", "pool4_objects", "pool_compact") + BIG_FORMS + ("pool1_jit",) + HOOK_POOL_FORMS
+GEN_FORMS = ("gen", "gen_candidates", "gen_between", "bup_candidates", "rbd_candidates", "lh_candidates", "playground_between")
+STAGED_FORMS = ("gen_candidates", "gen_between", "bup_candidates", "rbd_candidates", "lh_candidates", "playground_between")
+#: the forms whose step hook visits the agents in the order of the caller's actions dict: their stepping calls carry a `hook_order`;
+#: of these the pool forms are the ORDERED ones -- RedBlueDoors under failure mode "all", LockedHallway with own rewards, where the
+#: first toggler is treated differently (hook_states.CASES)
+ORDER_FORMS = ("rbd_candidates", "rbd_pool", "lh_candidates", "lh_pool", "lh12_pool")
+ORDERED_POOL_FORMS = ("rbd_pool", "lh_pool", "lh12_pool")
+RBD_FORMS = ("rbd_candidates", "rbd_pool")
+#: the env kinds whose step hook rewrites `aux` or reads a table in it (BlockedUnlockPickup's reads three constant bytes)
+HOOK_KINDS = ("redbluedoors", "lockedhallway", "rules")
 SPECS = {
     "plain": EnvSpec(8, 8, 3, 5, max_steps=12),
     "pool1": EnvSpec(5, 5, 2, 3, max_steps=6),
@@ -59,14 +86,26 @@ SPECS = {
     "big_objects1": EnvSpec(16, 16, 4, 7, max_steps=8),
     "plain_jit": EnvSpec(7, 6, 3, 5, max_steps=12),
     "pool1_jit": EnvSpec(6, 5, 2, 3, max_steps=6),
+    "rbd_candidates": EnvSpec(8, 4, 2, 3, max_steps=8, env_kind="redbluedoors"),
+    "rbd_pool": EnvSpec(12, 6, 2, 7, max_steps=24, failure_termination_mode="all", env_kind="redbluedoors"),
+    "lh_candidates": EnvSpec(13, 9, 2, 3, max_steps=8, joint_reward=True, env_kind="lockedhallway"),
+    "lh_pool": EnvSpec(13, 5, 2, 7, max_steps=24, env_kind="lockedhallway"),
+    "playground_between": EnvSpec(13, 7, 2, 3, max_steps=8),
+    "rules_pool": EnvSpec(9, 9, 2, 7, max_steps=24, failure_termination_mode="all", env_kind="rules"),
+    "lh12_pool": EnvSpec(10, 19, 3, 7, max_steps=24, env_kind="lockedhallway"),
 }
-FIRST_ENV = {"pool4_objects": 11, "gen_between": 11, "bup_candidates": 11}
+FIRST_ENV = {"pool4_objects": 11, "gen_between": 11, "bup_candidates": 11, "rbd_pool": 11, "lh_candidates": 11}
 #: the pool sizes a form alternates between when `pool_replace` gives it another K
 POOL_K = {"pool1": (1, 2), "pool4_objects": (4, 3), "pool_compact": (2, 3), "big_empty1": (1, 2), "big_objects1": (1, 2),
-          "pool1_jit": (1, 2)}
+          "pool1_jit": (1, 2),
+          # (the hook pools: eleven starts -- ten consecutive base states, every scenario of the kind among them, and the twin of one
+          # that differs from it in `aux` alone --, or ONE: the pool size at which set_layout_pool() and reset() arm the marker of an
+          # oracle-backed env, too)
+          "rbd_pool": (11, 1), "lh_pool": (11, 1), "rules_pool": (11, 1), "lh12_pool": (13, 1)}
 #: the commonest object type of a form's grids, what `q_select` scores by: the goal of the Empty layouts, a door where the grids are
 #: util.random_state's (three of its ten kinds of cell) and in BlockedUnlockPickup
 COMMON_TYPE = {f: (4 if f in ("plain", "plain_jit", "pool4_objects", "big_objects1", "bup_candidates") else 8) for f in SPECS}
+COMMON_TYPE.update({f: 4 for f in HOOK_FORMS}, rules_pool=6)           # (doors; the balls of the fetch-and-trap rules)
 #: (type, color, state) triples a cell edit writes: every cell format holds them, and an agent may stand on each (the edit may land
 #: under one): empty, floors, lava, a goal
 EDIT_CELLS = np.array([[1, 0, 0], [3, 3, 0], [3, 1, 0], [9, 0, 0], [8, 1, 0], [3, 4, 0]], np.uint8)
@@ -117,14 +156,17 @@ class SeqOracle(KeyOracle, DistOracle, KeyTableModel, SelectModel):
     shadow   the accounting's tensors as they must be, or None while it is off: updated HERE from what each stepping / restart launch
              hands back, by the sequential model -- not by the accounting calls the host logic makes, which it checks.  A restore
              takes the running trio of the rows it wrote from the env (the env copy is held to its own model elsewhere).
-    census   what happened: restarts by truncation / termination, a restored env that crossed an episode end, ...
+    census   what happened: restarts by truncation / termination, a restored env that crossed an episode end, ...; for the hook kinds
+             (HOOK_KINDS) what the step hooks met -- `_hook_census` --, whether a restore, a fork or a generated restart wrote
+             another `aux` than the env had, and where a visiting order decided an outcome
     Sub-shards of split() share the launcher: their rows are found by the storage offset of their `step_count` view."""
 
     def __init__(self, spec):
         super().__init__(spec)
         self.shadow, self.census, self.env = None, {}, None
         self._nested, self._faking = 0, False
-        self.restored = None
+        self.restored, self.forking = None, False        # (forking: apply() is inside env.fork(), whose copy is a restore)
+        self.ordered_launches = 0                        # (step launches that came with a visiting order)
 
     def attach(self, env):
         self.env = weakref.ref(env)
@@ -149,15 +191,59 @@ class SeqOracle(KeyOracle, DistOracle, KeyTableModel, SelectModel):
         dirs.copy_(torch.from_numpy(d))
 
     def step(self, B, grid, agents, rng, step_count, actions, target, err, obs, dirs, reward, terminated, truncated, **kw):
+        ar = kw.get("auto_reset")
+        self.ordered_launches += int(kw.get("hook_order") is not None)
         self._nested += 1
         try:
+            if self.spec.env_kind in HOOK_KINDS:
+                # (the fused form IS reset_done, then the step -- util.OracleBackend.step: taken apart here, so that the state the
+                # hook meets is at hand)
+                if ar is not None:
+                    self.reset_done(B, ar[0], ar[1], grid, agents, step_count, target, ar[2], ar[3])
+                kw = {k: v for k, v in kw.items() if k != "auto_reset"}
+                pre = {"grid": self._g3(grid).copy(), "agents": agents.numpy().copy(), "rng": rng.numpy().copy(),
+                       "step_count": step_count.numpy().copy(), "aux": target.numpy().copy()}
             super().step(B, grid, agents, rng, step_count, actions, target, err, obs, dirs, reward, terminated, truncated, **kw)
+            if self.spec.env_kind in HOOK_KINDS:
+                self._hook_census(pre, actions.numpy(), kw.get("hook_order"), self._g3(grid), agents.numpy(), target.numpy(),
+                                  reward.numpy(), terminated.numpy())
         finally:
             self._nested -= 1
         if self.shadow is not None and self._nested == 0:
-            ar = kw.get("auto_reset")
             model_stats(self._shadow_rows(self._rows(step_count, B)), reward.numpy(), terminated.numpy(), truncated.numpy(),
                         ar[3].numpy() if ar is not None else None, BEFORE if ar is not None else NONE)
+
+    def _hook_census(self, pre, act, hook_order, grid, agents, aux, reward, terminated):
+        """What one step of a hook kind went through, from the state before it (`pre`, behind the restarts of a fused step) and
+        after it; the event classes are those of tests/test_hook_states.py.  A step with a visiting order is taken once more on a
+        copy, in ascending order: the envs whose state or outputs differ are where the order decided something."""
+        B = act.shape[0]
+        b = np.arange(B)
+        self._count("aux_changed_by_a_step", (pre["aux"] != aux).any(axis=1).sum())
+        paid = reward > 0
+        if self.spec.env_kind == "redbluedoors":
+            self._count("hook_success", (paid & (act == hs.TOGGLE)).any(axis=1).sum())        # (no other toggle is paid)
+            self._count("hook_failure", ((pre["aux"][:, 4] == 0) & (aux[:, 4] == 1)).sum())    # (it leaves the stale flag behind)
+        if self.spec.env_kind == "rules":
+            want = pre["aux"][:, 2].astype(np.int64) | (pre["aux"][:, 3].astype(np.int64) << 8)
+            carry = agents[..., 5].astype(np.int64) | (agents[..., 6].astype(np.int64) << 8)
+            self._count("rule_carries_fired", ((carry == want[:, None]) & paid).any(axis=1).sum())
+            d = agents[..., 1] & 3
+            fx = agents[..., 2].astype(np.int64) + np.array([1, 0, -1, 0])[d]
+            fy = agents[..., 3].astype(np.int64) + np.array([0, 1, 0, -1])[d]
+            at = (act == hs.TOGGLE) & (fx == pre["aux"][:, None, 7]) & (fy == pre["aux"][:, None, 8])
+            door_open = (grid[b, pre["aux"][:, 8], pre["aux"][:, 7], 0] == hs.DOOR) & (grid[b, pre["aux"][:, 8], pre["aux"][:, 7], 2] == hs.OPEN)
+            newly = (pre["agents"][..., 4] == 0) & (agents[..., 4] != 0) & ~paid
+            self._count("rule_toggles_at_fired", (at & door_open[:, None] & newly).any(axis=1).sum())
+        if hook_order is None:
+            return
+        self._count("stepped_with_hook_order_while_tracking_episodes", int(self.shadow is not None))
+        c = {k: v.copy() for k, v in pre.items()}
+        out = ob.step_batch(self.d, c["grid"], c["agents"], c["rng"].view(np.uint64), c["step_count"], act, c["aux"], self.nthreads,
+                            hook_order=None)
+        differs = (c["grid"] != grid).any(axis=(1, 2, 3)) | (c["agents"] != agents).any(axis=(1, 2)) | (c["aux"] != aux).any(axis=1) \
+            | (out[2].view(np.int64) != reward.view(np.int64)).any(axis=1) | (out[3] != terminated).any(axis=1)
+        self._count("hook_order_changed_the_outcome", differs.sum())
 
     def _restarting(self, B, agents, step_count):
         """(before a done-based restart) who restarts, and why"""
@@ -185,6 +271,9 @@ class SeqOracle(KeyOracle, DistOracle, KeyTableModel, SelectModel):
     def reset_generate(self, B, gen, grid, agents, rng, step_count, aux, episode, was_reset):
         rows = self._restarting(B, agents, step_count)
         super().reset_generate(B, gen, grid, agents, rng, step_count, aux, episode, was_reset)
+        if aux is not None and (gen.get("stage") or {}).get("aux") is not None and not self._faking:
+            # (an episode end of a staged generator of a hook kind: on the device the adoption of a slot, its aux included)
+            self._count("adoption_of_a_slot_with_aux", (was_reset.bool() & (aux != 0).any(dim=1)).sum())
         self._restarted(rows, step_count, B, was_reset)
 
     def _as_done(self, sel, agents, step_count, call):
@@ -195,10 +284,14 @@ class SeqOracle(KeyOracle, DistOracle, KeyTableModel, SelectModel):
             self._faking = False
 
     def env_copy(self, n, src, src_rows, src_idx, dst, dst_rows, dst_idx, stage_tag, stage_mode, marker_fill, bad):
-        super().env_copy(n, src, src_rows, src_idx, dst, dst_rows, dst_idx, stage_tag, stage_mode, marker_fill, bad)
         env = self.env() if self.env is not None else None
-        if env is None or dst["cells"].data_ptr() != env._cells.data_ptr():
+        into_env = env is not None and dst["cells"].data_ptr() == env._cells.data_ptr()
+        old_aux = dst["aux"].clone() if into_env else None
+        super().env_copy(n, src, src_rows, src_idx, dst, dst_rows, dst_idx, stage_tag, stage_mode, marker_fill, bad)
+        if not into_env:
             return                                         # (a snapshot: the env is the source)
+        self._count("fork_copied_a_different_aux" if self.forking else "restore_wrote_a_different_aux",
+                    (old_aux != dst["aux"]).any(dim=1).sum())
         ids = np.arange(n) if dst_idx is None else dst_idx.numpy()
         self.restored[ids[(ids >= 0) & (ids < dst_rows)]] = True
         if dst.get("cur_length") is not None and src.get("cur_length") is None:
@@ -253,8 +346,43 @@ def small_pool(spec, K, r):
     return np.stack(gs), np.stack(ags), None
 
 
+#: per hook pool form: the scenario of hook_states.py whose start gets a twin, and what the twin's `aux` differs in
+TWIN_SCENARIO = {"rbd_pool": 3, "lh_pool": 1, "rules_pool": 0, "lh12_pool": 1}
+
+
+def hook_pool(form, K, r):
+    """K hook-dense starts of the form's case of tests/hook_states.py, WITH their aux: K consecutive base states (env b of a case
+    starts in scenario b % n: ten of them hold every scenario), the last replaced by a twin -- the cells and agent rows of one of
+    the others with another `aux`: RedBlueDoors, the open blue door without the stale flag (what the grid shows is true); Locked-
+    Hallway, the unlocked door's mask bit cleared; the rules, the success rule asking for the green ball.  Two envs on the pair are
+    equal in everything but hook state, and step differently.  K = 1: one base state."""
+    c = hs.case(HOOK_CASE[form])
+    assert c.spec == SPECS[form], f"form {form} is not on the spec of {c.name}"
+    lo = int(r.integers(0, hs.BASE - K))
+    idx = lo + np.arange(K)
+    g, a, x = (c.state[k][idx].copy() for k in ("grid", "agents", "aux"))
+    if K > 1:
+        j = int(np.flatnonzero(c.scenario[idx[:-1]] == TWIN_SCENARIO[form])[0])
+        g[-1], a[-1], x[-1] = g[j], a[j], x[j]
+        if form == "rbd_pool":
+            assert x[j, 4] == 1 and g[j, x[j, 1], x[j, 0], 2] == hs.OPEN
+            x[-1, 4] = 0
+        elif form == "lh_pool":
+            assert not x[j, 0] & 0x80 and x[j, 1], "an explicit aux with an unlocked door"
+            x[-1, 1] = 0
+        elif form == "lh12_pool":
+            assert x[j, 0] & 0x80 and (x[j, 1] or x[j, 2]), "a geometric aux with an unlocked door"
+            x[-1, 1:3] = 0
+        else:
+            x[-1] = layouts.rules_aux([("carries", hs.BALL, hs.GREEN, "success"), ("toggles_at", int(x[j, 7]), int(x[j, 8]), "failure", "open")])
+            assert (x[-1] != x[j]).any() and (x[-1, 7:9] == x[j, 7:9]).all()
+    return g, a, x
+
+
 def pool_content(form, K, r):
     """the pool a `pool_refill` / `pool_replace` installs"""
+    if form in HOOK_POOL_FORMS:
+        return hook_pool(form, K, r)
     if form in ("pool4_objects", "big_objects1"):
         return object_pool(SPECS[form], K, int(r.integers(1, 1 << 30)))
     return small_pool(SPECS[form], K, r)
@@ -291,6 +419,19 @@ def make_env(form, B, device="cpu", backend=None, specialise=False):
         env.set_layout_generator("blockedunlockpickup", layout_seed=5, room_size=6, staged="candidates", lead=4)
         env.reset(seed=3)
         assert env._gen["stage"]["candidates"] == 4
+    elif form in HOOK_POOL_FORMS:
+        env.set_layout_pool(*hook_pool(form, POOL_K[form][0], np.random.default_rng(11)))
+        env.reset(seed=3)
+    elif form in ("rbd_candidates", "lh_candidates"):          # (one candidate per env: these generators never draw from np_random)
+        env.set_layout_generator(form.split("_")[0].replace("rbd", "redbluedoors").replace("lh", "lockedhallway"), layout_seed=5,
+                                 room_size=5 if form == "lh_candidates" else 0, staged="candidates", lead=4)
+        env.reset(seed=3)
+        assert env._gen["stage"]["candidates"] == 1 and env._gen["stage"]["aux"] is not None
+    elif form == "playground_between":
+        env.set_layout_generator("playground", layout_seed=5, room_size=7, lead=4)     # (staged=True, the default: it must fall back)
+        env.reset(seed=3)
+        st = env._gen["stage"]
+        assert not st.get("candidates") and st["external"] == 2 and st["lead"] == 4, "Playground did not fall back to 'between'"
     else:
         staged = {"gen": False, "gen_candidates": "candidates", "gen_between": "between"}[form]
         env.set_layout_generator("empty_random", layout_seed=5, staged=staged, lead=4)
@@ -341,9 +482,14 @@ def make_ops(form, B, n_ops, seed, gpu=False, stretch=None, weights=None, kinds=
                  `without_queries()` of the list is the list of queries=False, arguments included; n_ops, `stretch` and every_third
                  count the other calls.  A `step_chains` directly in front of a query that goes through the env's `_row_set` is
                  not joined by apply(): the query carries first_consumer=True, and its own join() is what orders it behind the
-                 chains."""
-    r = np.random.default_rng([seed, B, (FORMS + BIG_FORMS + JIT_FORMS).index(form)])
-    rq = np.random.default_rng([seed, B, (FORMS + BIG_FORMS + JIT_FORMS).index(form), 1])
+                 chains.
+    The RedBlueDoors and LockedHallway forms (ORDER_FORMS): step, step_one_hot, step_chains, split, capture_replay and graph_again
+    carry a `hook_order` -- present about half the time, None otherwise --, drawn from a third generator (`rh`): step(hook_order=...)
+    leaves the bound hot path for the slow entry, with its marker bookkeeping, generator launches and accounting launch.  rollout
+    and persistent have no such parameter."""
+    r = np.random.default_rng([seed, B, SEED_ORDER.index(form)])
+    rq = np.random.default_rng([seed, B, SEED_ORDER.index(form), 1])
+    rh = np.random.default_rng([seed, B, SEED_ORDER.index(form), 2])
     spec = SPECS[form]
     A, H, W = spec.num_agents, spec.height, spec.width
     source = form not in PLAIN_FORMS
@@ -351,13 +497,16 @@ def make_ops(form, B, n_ops, seed, gpu=False, stretch=None, weights=None, kinds=
     w.update(weights or {})
     allowed = set(legal_kinds(form, B, gpu) + legal_query_kinds(form, B, gpu)) if kinds is None else set(kinds)
     S = {"tracking": None, "snaps": {}, "graphs": {}, "version": 0, "persistent": 0, "K": POOL_K.get(form, (0,))[0], "next_slot": 0,
-         "next_graph": 0, "staged": form in ("gen_candidates", "gen_between", "bup_candidates"),
+         "next_graph": 0, "staged": form in STAGED_FORMS,
          # (what the query layer keeps, from the calls' arguments alone: no draw of `r` depends on it)
          "epoch": 0, "touched": np.zeros(B, bool), "qgraphs": {}, "next_qgraph": 0, "last_table_ids": None}
 
     def actions(*lead):
         a = r.integers(0, 7, size=lead + (B, A)).astype(np.int8)
         a[r.random(lead + (B, A)) < 0.25] = 2                 # forward: episodes end by reaching something, too
+        if form in HOOK_POOL_FORMS:                           # (the starts stand in front of what their hook is about: toggle, pick up)
+            key = r.choice([5, 3], size=a.shape).astype(np.int8) if form == "rules_pool" else np.int8(5)
+            a = np.where(r.random(a.shape) < 0.35, key, a)
         return a
 
     def auto():
@@ -511,7 +660,7 @@ def make_ops(form, B, n_ops, seed, gpu=False, stretch=None, weights=None, kinds=
             q["points"] = pts
         return q
 
-    def draw_query(kind, pure, chained):
+    def draw_query(kind, pure, chained, fresh=False):
         op = {"kind": kind}
         if kind in ROW_QUERIES:
             e = q_ids()
@@ -551,6 +700,10 @@ def make_ops(form, B, n_ops, seed, gpu=False, stretch=None, weights=None, kinds=
             if not live:
                 return None
             op = dict(S["qgraphs"][int(rq.choice(live))]["op"], kind="q_graph_again")
+        if kind == "q_action_mask" and form in RBD_FORMS and rq.random() < 0.5:
+            op["ids"] = None      # (every row: the few envs whose stale door has a live agent in front of it are among them)
+        if fresh:                 # (every row, and a key without np_random -- the words differ from env to env: what can be equal is)
+            op.update(ids=None, rng=False)
         if kind in ROW_QUERIES:
             e = op["ids"]
             op["hits_touched"] = bool(S["touched"].all() if e is None else S["touched"][e].any())
@@ -564,9 +717,16 @@ def make_ops(form, B, n_ops, seed, gpu=False, stretch=None, weights=None, kinds=
         if not queries:
             return []
         chained = prev["kind"] == "step_chains"
-        n = max(int(rq.choice(3, p=QUERY_COUNT_P)), 1 if chained else 0)
+        # a hook pool form behind a reset(): the envs just restarted stand on their starts, those on a start and on its twin (hook_pool)
+        # equal in everything but aux -- the first query is a state_key of the whole batch
+        fresh = form in HOOK_POOL_FORMS and prev["kind"] == "reset" and "q_state_key" in allowed
+        n = max(int(rq.choice(3, p=QUERY_COUNT_P)), 1 if chained or fresh else 0)
         out = []
         for j in range(n):
+            if fresh and j == 0:
+                out.append(draw_query("q_state_key", pure, False, fresh=True))
+                qran["q_state_key"] = qran.get("q_state_key", 0) + 1
+                continue
             first = chained and j == 0
             names = sorted(k for k in allowed if k in QUERY_KINDS and (not pure or k in PURE_KINDS)
                            and (not first or k in (FIRST_CONSUMERS if not pure else ROW_QUERIES + ("q_select",))))
@@ -616,10 +776,29 @@ def make_ops(form, B, n_ops, seed, gpu=False, stretch=None, weights=None, kinds=
         ran[op["kind"]] = ran.get(op["kind"], 0) + 1
         return op
 
+    def with_order(op):
+        """the visiting order of a stepping call of an ORDER_FORMS form: u8[B,A] (or [T,B,A]) permutations, or None -- every draw is
+        one of `rh`, and no other form's call gets the key"""
+        def order(*lead):
+            if rh.random() < 0.5:
+                return None
+            return np.argsort(rh.random(lead + (B, A)), axis=-1).astype(np.uint8)
+        k = op["kind"]
+        if k in ("step", "step_one_hot", "step_chains"):
+            op["hook_order"] = order()
+        elif k in ("capture_replay", "split"):
+            op["hook_order"] = order(op["acts"].shape[0])
+            if k == "capture_replay" and op["keep"] is not None:
+                S["graphs"][op["keep"]]["hook_order"] = op["hook_order"]
+        elif k == "graph_again":                              # (the graph reads the order it was captured with)
+            op["hook_order"] = S["graphs"][op["graph"]]["hook_order"]
+
     ops, ran, qran = [], {}, {}
     for i in range(n_ops):
         pure = stretch is not None and stretch[0] < i < stretch[1]
         op = main_op(i, pure)
+        if form in ORDER_FORMS:
+            with_order(op)
         ops.append(op)
         note(op)
         ops.extend(draw_queries(op, pure or op["kind"] == "tm_begin"))     # (behind the snapshot: part of what is repeated)
@@ -640,7 +819,8 @@ def describe(op) -> str:
 # ---- performing a call --------------------------------------------------------------------------------------------------------------
 
 def new_ctx():
-    return {"snaps": {}, "graphs": {}, "tm": None, "outs": {}, "table": None, "selector": None, "qgraphs": {}, "warm_table": None}
+    return {"snaps": {}, "graphs": {}, "tm": None, "outs": {}, "table": None, "selector": None, "qgraphs": {}, "warm_table": None,
+            "seen": {}}                                        # (seen: what apply() itself met, on either kind of env)
 
 
 def is_hip(env) -> bool:
@@ -648,6 +828,28 @@ def is_hip(env) -> bool:
 
 
 def apply(env, op, ctx, nxt=None) -> dict:
+    """`perform()`, and what two envs that share a fault of the host logic cannot show each other: a stepping call's visiting order
+    reached every launch it stands for (an oracle-backed env: the launcher counts them), and a pool call installed the aux it was
+    given."""
+    be = env.backend
+    ho, before = op.get("hook_order"), getattr(be, "ordered_launches", None)
+    outs = perform(env, op, ctx, nxt)
+    if ho is not None and before is not None:
+        k = op["kind"]
+        want = {"capture_replay": 2 * len(op["acts"]), "graph_again": len(op["acts"]), "split": int(np.sum(op.get("steps", 0)))}.get(k, 1)
+        assert be.ordered_launches - before == want, \
+            f"{describe(op)}: {be.ordered_launches - before} launch(es) got the visiting order, {want} stand for the call"
+    if op["kind"] in ("pool_refill", "pool_replace"):
+        pool = env._pool
+        assert (pool[2] is None) == (op["aux"] is None), f"{describe(op)}: the pool's aux"
+        assert torch.equal(pool[0].cpu(), torch.from_numpy(layouts.pack_cells_for(env.spec, op["grids"]))) \
+            and torch.equal(pool[1].cpu(), torch.from_numpy(op["agents"])) \
+            and (pool[2] is None or torch.equal(pool[2].cpu(), torch.from_numpy(op["aux"]))), \
+            f"{describe(op)}: the pool does not hold the layouts, agent rows and aux it was given"
+    return outs
+
+
+def perform(env, op, ctx, nxt=None) -> dict:
     """One call on `env`.  Returns what the call wrote or handed back that is not part of the env state: name -> tensor (the env's
     own output buffers by name, a rollout's dict and a query's answers under 'out.<key>').  nxt: the call that follows in the list
     (`following`), which decides the shape of a step_chains."""
@@ -661,17 +863,22 @@ def apply(env, op, ctx, nxt=None) -> dict:
         names = (("_one_hot",) if one_hot else ("obs",)) + OUTPUTS[1:] + (("was_reset",) if auto_reset else ())
         return {n: getattr(env, n) for n in names}
 
-    def steps(acts, auto_reset, times=1):
+    def steps(acts, auto_reset, times=1, order=None):
         for _ in range(times):
             for t in range(acts.shape[0]):
-                env.step(dv(acts[t]), auto_reset=auto_reset)
+                env.step(dv(acts[t]), auto_reset=auto_reset, hook_order=None if order is None else dv(order[t]))
         return outputs(auto_reset)
 
+    ho = op.get("hook_order")                                  # (a stepping call of the ORDER_FORMS: u8[B,A], u8[T,B,A] or None)
+    if ho is not None and env._mark["armed"]:
+        ctx["seen"]["stepped_with_hook_order_while_armed"] = ctx["seen"].get("stepped_with_hook_order_while_armed", 0) + 1
+        if isinstance(be, SeqOracle):
+            be._count("stepped_with_hook_order_while_armed")
     if kind == "step":
-        env.step(dv(op["acts"]), auto_reset=op["auto_reset"])
+        env.step(dv(op["acts"]), auto_reset=op["auto_reset"], hook_order=dv(ho))
         return outputs(op["auto_reset"])
     if kind == "step_one_hot":
-        env.step(dv(op["acts"]), auto_reset=op["auto_reset"], one_hot=True)
+        env.step(dv(op["acts"]), auto_reset=op["auto_reset"], one_hot=True, hook_order=dv(ho))
         return outputs(op["auto_reset"], one_hot=True)
     if kind == "rollout":
         return {"out." + k: v for k, v in env.rollout(dv(op["acts"]), auto_reset=op["auto_reset"]).items()}
@@ -695,7 +902,11 @@ def apply(env, op, ctx, nxt=None) -> dict:
         env.restore(ctx["snaps"][op["slot"]], dv(op["env_ids"]), dv(op["rows"]), check=op["check"])
         return {}
     if kind == "fork":
+        if isinstance(be, SeqOracle):
+            be.forking = True
         env.fork(dv(op["src"]), dv(op["dst"]), check=op["check"])
+        if isinstance(be, SeqOracle):
+            be.forking = False
         return {}
     if kind == "edit":
         cells = env.cells                                      # (the public tensor: handing it out takes the marker's promise back)
@@ -746,7 +957,7 @@ def apply(env, op, ctx, nxt=None) -> dict:
         for c, n in zip(children, op["steps"]):
             lo, hi = c._range
             for t in range(int(n)):
-                c.step(dv(op["acts"][t, lo:hi]), auto_reset=op["auto_reset"])
+                c.step(dv(op["acts"][t, lo:hi]), auto_reset=op["auto_reset"], hook_order=None if ho is None else dv(ho[t, lo:hi]))
                 invariants(c, f"sub-shard [{lo}, {hi}) step {t}")
         return outputs(op["auto_reset"])
     # ---- the GPU-only kinds, and what they are on the oracle
@@ -754,15 +965,15 @@ def apply(env, op, ctx, nxt=None) -> dict:
         if not hip:
             if op["keep"] is not None:
                 ctx["graphs"][op["keep"]] = True
-            return steps(op["acts"], op["auto_reset"], times=2)
-        graph = env.capture_steps(dv(op["acts"]), auto_reset=op["auto_reset"], sub_shards=op["sub_shards"])
+            return steps(op["acts"], op["auto_reset"], times=2, order=ho)
+        graph = env.capture_steps(dv(op["acts"]), auto_reset=op["auto_reset"], sub_shards=op["sub_shards"], hook_order=dv(ho))
         graph.replay(); graph.replay()
         if op["keep"] is not None:
             ctx["graphs"][op["keep"]] = graph
         return outputs(op["auto_reset"])
     if kind == "graph_again":
         if not hip:
-            return steps(op["acts"], op["auto_reset"])
+            return steps(op["acts"], op["auto_reset"], order=ho)
         ctx["graphs"][op["graph"]].replay()
         return outputs(op["auto_reset"])
     if kind == "persistent":
@@ -775,8 +986,8 @@ def apply(env, op, ctx, nxt=None) -> dict:
         return outputs(op["auto_reset"])
     if kind == "step_chains":
         if not hip:
-            return steps(op["acts"][None], op["auto_reset"])
-        env.step(dv(op["acts"]), auto_reset=op["auto_reset"], sub_shards=2)
+            return steps(op["acts"][None], op["auto_reset"], order=None if ho is None else ho[None])
+        env.step(dv(op["acts"]), auto_reset=op["auto_reset"], sub_shards=2, hook_order=dv(ho))
         if unjoined(op, nxt):                                  # (the query that follows joins: nothing may read this env before it)
             return {}
         env.join()
@@ -823,15 +1034,38 @@ def apply_query(env, op, ctx) -> dict:
         idx = dv(a["ids"])
         n = n_rows if idx is None else int(idx.shape[0])
         keep = a.get("keep_out", False)
+        t = None
+        if isinstance(be, SeqOracle) and sp.env_kind in HOOK_KINDS:     # (the rows the query names, for the census of what it met)
+            t = target.tensors if target is not env else {"cells": env._cells, "agents": env.agents, "rng": env.rng,
+                                                           "step_count": env.step_count, "aux": env.aux}
+            t = {m: (v if idx is None else v[idx]).numpy() for m, v in t.items() if m in ("cells", "agents", "rng", "step_count", "aux")}
         if which == "key":
             out = kept("key", (n,), torch.int64, 0) if keep else None
-            return target.state_key(idx, salt=a["salt"], step_count=a["step_count"], rng=a["rng"], out=out)
+            res = target.state_key(idx, salt=a["salt"], step_count=a["step_count"], rng=a["rng"], out=out)
+            if t is not None:
+                # two rows equal in cells, agents and whatever else the key covers, but for `aux`: their keys must differ
+                first = {}
+                for i in range(n):
+                    rest = t["cells"][i].tobytes() + t["agents"][i].tobytes() + (t["step_count"][i].tobytes() if a["step_count"] else b"") \
+                        + (t["rng"][i].tobytes() if a["rng"] else b"")
+                    j = first.setdefault(rest, i)
+                    if t["aux"][j].tobytes() != t["aux"][i].tobytes():
+                        assert int(res[i]) != int(res[j]), f"rows {j} and {i} differ in hook state only, and have one state key"
+                        seen("state_keys_differ_by_hook_state_only")
+            return res
         if which == "mask":
             shape, dt = ((n, A, 7), torch.bool) if a["expand"] else ((n, A), torch.uint8)
             res = target.action_mask(idx, expand=a["expand"], out=kept("mask", shape, dt, 0) if keep else None)
             if isinstance(be, SeqOracle):
                 bits = res[..., 2:6] if a["expand"] else ((res[..., None].to(torch.int32) >> torch.arange(2, 6)) & 1).bool()
                 seen("mask_with_a_clear_and_a_set_bit_beyond_the_turns", int(bool(bits.any()) and not bool(bits.all())))
+            if t is not None and sp.env_kind == "redbluedoors":
+                # a live agent in front of the blue door while the stale flag is up: the door's object is closed, whatever the
+                # grid shows there (a failed opening, an edit over the door)
+                d = t["agents"][..., 1] & 3
+                fx, fy = t["agents"][..., 2] + np.array([1, 0, -1, 0])[d], t["agents"][..., 3] + np.array([0, 1, 0, -1])[d]
+                at = (t["agents"][..., 4] == 0) & (fx == t["aux"][:, None, 0]) & (fy == t["aux"][:, None, 1])
+                seen("mask_of_a_stale_door", int(((t["aux"][:, 4] == 1) & at.any(axis=1)).sum()))
             return res
         field = a["field"]
         out = kept("dist", (n, H, W) if field else (n, A), torch.int16, -1) if keep else None
@@ -840,6 +1074,9 @@ def apply_query(env, op, ctx) -> dict:
             avoid_lava=a["avoid_lava"], out=out)
         if isinstance(be, SeqOracle) and not field and bool((res < 0).any()) and bool((res >= 0).any()):
             seen("agent_distance_with_and_without_a_way")
+        if t is not None and sp.env_kind == "lockedhallway":      # (doors that the agents' keys have opened, or a start shows open)
+            g3 = layouts.unpack_cells_for(sp, t["cells"])
+            seen("distance_over_a_grid_with_an_open_door", int(((g3[..., 0] == hs.DOOR) & (g3[..., 2] == hs.OPEN)).any(axis=(1, 2)).sum()))
         return res
 
     def table():
@@ -1077,9 +1314,42 @@ def census_of(ops_lists, oracles) -> dict:
     return c
 
 
+_AUX = ["aux_changed_by_a_step", "restore_wrote_a_different_aux", "fork_copied_a_different_aux",
+        "stepped_with_hook_order_while_tracking_episodes"]
+#: what a hook form's seeds must have met, beside what every form must (conditions on the lists and pools: the oracle alone meets
+#: them).  Not asked, because the form cannot reach it:
+#:   playground_between   nothing of this: its kind is hook-free, it has no aux and its calls carry no visiting order
+#:   rules_pool           the visiting-order items: the declared rules are evaluated per agent, and its calls carry no order;
+#:                        its `aux` is the rule table, which no step rewrites: two envs differ in it by their layouts (the twin)
+#:   the generator forms  hook_order_changed_the_outcome (the default failure mode and a joint reward are symmetric in the order
+#:                        but for RedBlueDoors' first failing toggler, which two agents in a 2 x 4 room seldom reach together),
+#:                        and the marker item: a generator env is never armed
+HOOK_NEED = {
+    "rbd_candidates": _AUX + ["adoption_of_a_slot_with_aux", "hook_success", "hook_failure"],
+    # (a generated LockedHallway of this size has the geometric aux -- the same bytes in every env -- until a door is unlocked, which
+    # takes a key fetched and carried to its door: more than the 8 steps of an episode.  No step of a random walk rewrites it, and
+    # no copy writes another: measured on the oracle, 0 of 4 lists.  LockedHallway's hook state is lh_pool's to show.)
+    "lh_candidates": ["adoption_of_a_slot_with_aux", "stepped_with_hook_order_while_tracking_episodes"],
+    "rbd_pool": _AUX + ["hook_success", "hook_failure", "hook_order_changed_the_outcome", "stepped_with_hook_order_while_armed"],
+    "lh_pool": _AUX + ["hook_order_changed_the_outcome", "stepped_with_hook_order_while_armed"],
+    "lh12_pool": _AUX + ["hook_order_changed_the_outcome", "stepped_with_hook_order_while_armed"],
+    "rules_pool": ["restore_wrote_a_different_aux", "fork_copied_a_different_aux", "rule_carries_fired", "rule_toggles_at_fired"],
+}
+#: the same for the query layer.  state_keys_differ_by_hook_state_only needs two rows equal in cells and agents: the pool forms have
+#: the twin; a generated env changes its aux only together with its cells (not asked of the generator forms).  A stale door in front
+#: of a live agent: RedBlueDoors only
+HOOK_QUERY_NEED = {
+    "rbd_candidates": ["mask_of_a_stale_door"],
+    "rbd_pool": ["state_keys_differ_by_hook_state_only", "mask_of_a_stale_door"],
+    "lh_pool": ["state_keys_differ_by_hook_state_only", "distance_over_a_grid_with_an_open_door"],
+    "lh12_pool": ["state_keys_differ_by_hook_state_only", "distance_over_a_grid_with_an_open_door"],
+    "rules_pool": ["state_keys_differ_by_hook_state_only"],
+}
+
+
 def assert_census(c, form, B, gpu=False, queries=False):
     """Every legal kind at least three times (a GPU-only kind: at least once); the restarts, restores and switches that the
-    cross-feature rules are about at least once.  queries: the same for the query kinds, and what the query layer is there to meet
+    cross-feature rules are about at least once; for a hook form, HOOK_NEED (and with queries HOOK_QUERY_NEED).  queries: the same for the query kinds, and what the query layer is there to meet
     -- a row query of an env just restored, reset or edited; a snapshot queried after the pool or the state changed under it; an
     insert of new and known keys, a lookup that misses; a selection cut inside a tie and one padded; distances with and without a
     way in one answer; a mask with a clear and a set bit beyond the turns; with the chains, two queries that are their first
@@ -1090,8 +1360,11 @@ def assert_census(c, form, B, gpu=False, queries=False):
     need = ["restore_with_repeated_rows", "tracking_on_off_on", "restored_row_without_the_running_episode"]
     if form not in PLAIN_FORMS:                               # (no restart source: a finished env stays finished)
         need += ["restart_by_truncation", "restored_env_crossed_an_episode_end"]
-        if form != "bup_candidates":                          # (the box behind the locked door: no random walk of 8 steps picks it up)
+        # (the box behind the locked door: no random walk of 8 steps picks it up; nor does one unlock every door of a generated
+        # LockedHallway, or find a goal on a Playground, which has none: measured on the oracle, 390 of 390 restarts truncations)
+        if form not in ("bup_candidates", "lh_candidates", "playground_between"):
             need.append("restart_by_termination")
+    need += HOOK_NEED.get(form, [])
     for k in need:
         assert c.get(k, 0) >= 1, f"form {form}: {k} never happened: {c}"
     if not queries:
@@ -1102,6 +1375,7 @@ def assert_census(c, form, B, gpu=False, queries=False):
     need = {"row_query_of_an_env_restored_reset_or_edited_since_the_last": 1, "snapshot_query_older_than_a_pool_or_state_change": 1,
             "insert_of_new_and_known_keys": 1, "lookup_with_a_miss": 1, "select_cut_inside_a_tie": 1, "select_padded": 1,
             "agent_distance_with_and_without_a_way": 1, "mask_with_a_clear_and_a_set_bit_beyond_the_turns": 1}
+    need.update({k: 1 for k in HOOK_QUERY_NEED.get(form, [])})
     if gpu and B >= 128:
         need["query_as_first_consumer_of_the_chains"] = 2
     for k, n in need.items():
@@ -1239,8 +1513,103 @@ def pinned_generated_rollout_of_unaligned_steps():
     return {"form": form, "B": B, "ops": ops}
 
 
+def _order(B, A, seed, *lead):
+    return np.argsort(np.random.default_rng([seed, 98]).random(lead + (B, A)), axis=-1).astype(np.uint8)
+
+
+def _toggles(form, B, seed, auto_reset=False, order=True, p=0.8):
+    """a step in which most agents toggle what they face (the hook pools' starts face their doors), in a visiting order"""
+    a = _acts(form, B, seed)
+    a[np.random.default_rng([seed, 97]).random(a.shape) < p] = hs.TOGGLE
+    return {"kind": "step", "acts": a, "auto_reset": auto_reset, "hook_order": _order(B, a.shape[1], seed) if order else None}
+
+
+def pinned_restore_of_a_changed_aux():
+    """RedBlueDoors: a snapshot of fresh starts, a step of toggles that rewrites aux (the failed openings raise the stale flag, the
+    toggles at a stale door lower it), a restore of every other env, and the same toggles again: what they do depends on the flag --
+    a restore that left aux as it was would show in that step"""
+    form, B = "rbd_pool", 130
+    ids = np.arange(0, B, 2)
+    kept = {}
+
+    def rewritten(env, where):
+        kept["aux"] = env.aux.cpu().clone()
+        assert int((kept["aux"][:, 4] != kept["start"][:, 4]).sum()) >= 8, f"{where}: the step did not rewrite the stale flags"
+
+    def start(env, where):
+        kept["start"] = env.aux.cpu().clone()
+
+    def restored(env, where):
+        aux, t = env.aux.cpu(), torch.from_numpy(ids)
+        assert torch.equal(aux[t], kept["start"][t]) and not torch.equal(aux[t], kept["aux"][t]), f"{where}: aux of the restored envs"
+        others = torch.from_numpy(np.arange(1, B, 2))
+        assert torch.equal(aux[others], kept["aux"][others]), f"{where}: aux of the other envs"
+    ops = [{"kind": "reset", "seed": 5, "mask": None}, _snapshot(0), _toggles(form, B, 1), _restore(0, ids, ids), _toggles(form, B, 1),
+           _toggles(form, B, 2, auto_reset=True), _toggles(form, B, 3, auto_reset=True, order=False)]
+    return {"form": form, "B": B, "ops": ops, "checks": {1: start, 2: rewritten, 3: restored}}
+
+
+def pinned_reset_between_launch_and_adoption():
+    """LockedHallway with one candidate per env: reset(seed, mask) between the generator launch that made the candidates (every
+    lead / 2 = 2 steps) and the truncation at 8 that would adopt them -- the chosen envs' episode counters moved on, their slots are
+    stale, and the adoption must not take them; the steps come with and without a visiting order"""
+    form, B = "lh_candidates", 130
+
+    def launched(env, where):
+        if is_hip(env):                                       # (the oracle generates in place: it keeps no slots)
+            assert bool((env._gen["stage"]["tag"] != -1).any()), f"{where}: no candidate has been made yet"
+    ops = [_toggles(form, B, 1, auto_reset=True, p=0.2), _step(form, B, 2), _toggles(form, B, 3, auto_reset=True, p=0.2), _step(form, B, 4),
+           {"kind": "reset", "seed": 9, "mask": (np.arange(B) % 3 == 0).astype(np.uint8)}, _step(form, B, 5),
+           {"kind": "reset", "seed": None, "mask": np.arange(B) % 5 == 0}]
+    ops += [_toggles(form, B, 6 + t, auto_reset=True, order=bool(t % 2), p=0.2) for t in range(9)]
+    return {"form": form, "B": B, "ops": ops, "checks": {3: launched}}
+
+
+def pinned_hook_order_after_hot_path_steps():
+    """step(hook_order=...) directly behind steps of the bound hot-path entry on an armed pool: the visiting order sends the call
+    through the slow entry, which must keep (auto_reset: the tracked step) or take back (no auto_reset) the marker's promise itself"""
+    form, B = "rbd_pool", 130
+
+    def armed(env, where):
+        if is_hip(env):                                       # (an oracle-backed env has no tracked step: only a one-layout pool arms it)
+            assert env._mark["armed"] and env._bound.get((True, False), (0, 0, False))[2], f"{where}: not armed by a tracked hot-path step"
+
+    def disarmed(env, where):
+        assert not env._mark["armed"] and bool((env._marker == -1).all()), where
+    ops = [_toggles(form, B, 1, auto_reset=True, order=False), _toggles(form, B, 2, auto_reset=True, order=False),
+           _toggles(form, B, 3, auto_reset=True, order=False), _toggles(form, B, 4, auto_reset=True), _toggles(form, B, 5, auto_reset=True, order=False),
+           _toggles(form, B, 6, auto_reset=True), _toggles(form, B, 7), _toggles(form, B, 8, auto_reset=True, order=False),
+           _toggles(form, B, 9, auto_reset=True)]
+    return {"form": form, "B": B, "ops": ops, "checks": {2: armed, 3: armed, 4: armed, 6: disarmed}}
+
+
+def pinned_load_state_dict_of_a_hook_pool():
+    """load_state_dict of a hook pool form -- the pool's aux travels in the dict --, then auto-reset steps: the envs that restart
+    take their layout's aux -- the door positions and the stale flag -- with its cells"""
+    form, B = "rbd_pool", 130
+    kept = {}
+
+    def before(env, where):
+        kept["pool_aux"], kept["aux"] = env._pool[2].cpu().clone(), env.aux.cpu().clone()
+        assert bool(kept["pool_aux"].any()) and len({bytes(r) for r in kept["pool_aux"].numpy()}) > 1, where
+
+    def restarted(env, where):
+        assert int(env.was_reset.sum()) > 0, f"{where}: no env restarted from the loaded pool"
+
+    def loaded(env, where):
+        assert env._pool[2] is not None and torch.equal(env._pool[2].cpu(), kept["pool_aux"]), f"{where}: the pool's aux"
+        assert torch.equal(env.aux.cpu(), kept["aux"]), f"{where}: the envs' aux"
+    ops = [_toggles(form, B, 1), _toggles(form, B, 2), {"kind": "load_state_dict"}, _toggles(form, B, 3, auto_reset=True),
+           _toggles(form, B, 4, auto_reset=True, order=False), _toggles(form, B, 5, auto_reset=True), _toggles(form, B, 6, auto_reset=True)]
+    return {"form": form, "B": B, "ops": ops, "checks": {1: before, 2: loaded, 3: restarted}}
+
+
 PINNED = {"edit_then_step": pinned_edit_then_step, "generated_rollout_of_unaligned_steps": pinned_generated_rollout_of_unaligned_steps, "armed_snapshot_after_cells": pinned_armed_snapshot_after_cells,
           "restore_after_refill": pinned_restore_after_refill, "restore_before_an_adoption": pinned_restore_before_an_adoption,
           "restore_before_an_adoption_candidates": pinned_restore_before_an_adoption_candidates,
           "track_between_hot_path_steps": pinned_track_between_hot_path_steps,
-          "load_state_dict_stages_the_generator": pinned_load_state_dict_stages_the_generator}
+          "load_state_dict_stages_the_generator": pinned_load_state_dict_stages_the_generator,
+          "restore_of_a_changed_aux": pinned_restore_of_a_changed_aux,
+          "reset_between_launch_and_adoption": pinned_reset_between_launch_and_adoption,
+          "hook_order_after_hot_path_steps": pinned_hook_order_after_hot_path_steps,
+          "load_state_dict_of_a_hook_pool": pinned_load_state_dict_of_a_hook_pool}

@@ -19,7 +19,37 @@ written for it.  Here the calls come in arbitrary order:
     a query leaves every byte of env state, engine state, kept snapshots, the marker and its host flag alone (the fingerprint);
     a row query's answer is what the launcher gives on the rows it should have read -- the live `_cells` / agents / ... or the
     snapshot's own tensors --, asked for directly (two envs that share a fault of the host logic agree with each other).
-tests/test_env_sequences_gpu.py runs the same lists on the HIP backend against this oracle."""
+  * the hook forms (es.HOOK_FORMS: RedBlueDoors, LockedHallway, Playground's generator, the declared rules): the same four tests,
+    with a census of their own (es.HOOK_NEED, es.HOOK_QUERY_NEED) -- hook successes and failures, aux rewritten by a step, a restore
+    and a fork that wrote another aux, generated restarts that carry one, steps with a visiting order while the marker is armed and
+    while the accounting runs, outcomes the order decided, state keys that differ by hook state only, masks of a stale door -- and
+    two checks in es.apply() that two envs sharing a fault cannot give each other: every launch a stepping call stands for received
+    its visiting order, and a pool call installed the aux it was given.
+tests/test_env_sequences_gpu.py runs the same lists on the HIP backend against this oracle.
+
+Recorded host-logic mutants of multigrid_amd/batched.py for the hook forms (none committed, all in bounds), this file run once against
+each (126 tests: the form lh12_pool came after these runs; no GPU run):
+
+  (a) `snapshot()` leaves `aux` out of the members it copies (the snapshot keeps zeros).
+      Dies: 6 failed, 120 passed.  The time machine of bup_candidates, rbd_candidates, lh_candidates, lh_pool and rules_pool (the
+      repeated stretch differs: a state key, a termination, a reward) and the pinned case restore_of_a_changed_aux ("aux of the
+      restored envs").  Every sequence and census case passes, as they must: both envs forget the same bytes.  rbd_pool's time
+      machine passed (why was not looked into); the pinned case is RedBlueDoors'.
+  (b) the adoption has no aux to copy: the candidate slots (`_gen["stage"]["aux"]`) are not made.
+      Dies, but only by the assertion of es.make_env that the slots of rbd_candidates and lh_candidates hold an aux (13 failed: every
+      test of these two forms and the pinned case reset_between_launch_and_adoption).  What the mutant is about cannot show here:
+      the oracle generates in place and adopts nothing.  It is tests/test_env_sequences_gpu.py that holds the adopted aux to the
+      oracle's, byte for byte after every call (not run against the mutant).
+  (c) the slow path of `step` drops `hook_order` when sub_shards > 1 or while the marker is armed.
+      As the driver stood first: SURVIVED, the 47 tests of the hook forms and the pinned cases passed -- both envs drop the same
+      order, and the census counts calls, not what a launch received.  es.apply() now counts the launches that got a visiting
+      order against those the call stands for, and kills it: 10 failed -- the sequences of rbd_pool (4 of 4) and lh_pool (2 of 4: the
+      lists that step with an order while a one-layout pool has the marker armed), their census and time machine ("0 launch(es) got
+      the visiting order, 1 stand for the call"; split(): 2 of 3).
+  (d) `set_layout_pool` ignores `auxs` on an in-place refill.
+      As the driver stood first: SURVIVED, the same 47 passed, census included -- the old pool's aux are hook-dense too.  es.apply()
+      now holds the pool to the layouts, agent rows and aux of the call, and kills it: 18 failed, every sequence, census and time
+      machine case of rbd_pool, lh_pool and rules_pool, at their first pool_refill."""
 import functools
 
 import numpy as np

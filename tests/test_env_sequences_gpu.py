@@ -16,6 +16,12 @@ oracle-backed envs: tests/test_env_sequences.py).
     is the chains' first consumer, and nothing here reads the HIP env in between.  What the twin cannot show, because it runs the
     same host logic, is asserted on the HIP env's host state: a query leaves `_mark["armed"]` as it was and `_chains_pending` off,
     and a snapshot's rows answer as the launcher does over the snapshot's own tensors (test_env_sequences.asked_directly).
+  * the hook forms (es.HOOK_FORMS): RedBlueDoors, LockedHallway, Playground's generator and the declared rules through the same lists
+    -- `aux` is among the members compared after every call, so an adoption, a restore or a pool restart that loses hook state
+    shows here; the stepping calls of the RedBlueDoors and LockedHallway forms come with a visiting order through step(), step(
+    sub_shards=2), split() children and capture_steps(sub_shards=1 or 2).  Asserted on the HIP env: a restore / reset(mask) / seed
+    met a live slot (the three generator forms), auto-reset steps ran the tracked entry (the pool forms), and a step with a
+    visiting order met an armed marker (rbd_pool, lh_pool).  The mutants tried for these forms: tests/test_env_sequences.py.
 
 Recorded host-logic mutants of multigrid_amd/batched.py (none committed, none touches a kernel, all in bounds), each tried on both
 sequence files, one run each:
@@ -99,6 +105,7 @@ def sequence(form, B, seed):
         es.compare(hip, twin, ch, ct, where, oh, ot)
         ent = hip._bound.get((True, False))
         seen["tracked_entry"] = seen["tracked_entry"] or bool(ent and ent[2])
+    seen["order_while_armed"] = ch["seen"].get("stepped_with_hook_order_while_armed", 0)      # (counted on the HIP env's own flag)
     return ops, twin.backend, seen
 
 
@@ -130,10 +137,12 @@ def test_census(form):
     runs = [sequence(form, B, seed) for B, seed in SEQUENCES]
     c = es.census_of([r[0] for r in runs], [r[1] for r in runs])
     es.assert_census(c, form, 130, gpu=True, queries=True)
-    if form in ("gen_candidates", "gen_between", "bup_candidates"):
+    if form in ("gen_candidates", "gen_between", "bup_candidates", "rbd_candidates", "lh_candidates", "playground_between"):
         assert sum(r[2]["live_slots"] for r in runs) > 0, "no restore / reset(mask) / seed met a live staging slot"
-    if form in ("pool1", "pool4_objects"):
+    if form in ("pool1", "pool4_objects") + es.HOOK_POOL_FORMS:
         assert any(r[2]["tracked_entry"] for r in runs), "step(auto_reset=True) never ran through the tracked hot-path entry"
+    if form in es.ORDERED_POOL_FORMS:       # (here the marker is armed by the tracked steps themselves, at every pool size)
+        assert sum(r[2]["order_while_armed"] for r in runs) > 0, "no step with a visiting order met an armed layout marker"
 
 
 @pytest.mark.parametrize("form", es.FORMS)
