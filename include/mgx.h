@@ -671,6 +671,42 @@ int mgx_render_atlas(int32_t tile_size, uint8_t *atlas, void *stream);
 int mgx_render(const MgxSpec *spec, int64_t n, const MgxCell *grid, const uint8_t *agents, const uint8_t *obs, const uint8_t *atlas,
                int32_t tile_size, uint8_t *frames, void *stream);
 
+/* VIEW FRAMES (additive to ABI 11): every agent's own view as pixels -- the partial RGB observation MiniGrid users know as
+ * RGBImgPartialObsWrapper / get_frame(agent_pov=True).  Build-defined: the reference refuses it for several agents
+ * (get_pov_render, multigrid/base.py), but the rule below is what its own Grid.render draws when it is handed the view as a
+ * v x v Grid, the agents in it as Agents and the seen cells as the highlight mask (tests/golden/render/view_frames.npz).
+ *
+ * A view frame is u8[v*ts, v*ts, 3].  Pixel (py, px) belongs to view cell (i, j) = (px / ts, py / ts) of image[i, j] -- the placement
+ * Grid.render uses (grid.py:291-306).  The viewer sits at (v / 2, v - 1) and faces up.  A cell's tile is the atlas tile
+ * render_key(appearance, overlay, highlight) (csrc/mgx_render.h: render_view_key):
+ *   appearance   of the cell's (type, color, state) exactly as the full frame computes it: unseen, empty, agent and every
+ *                out-of-range byte draw no object; a box draws the same whatever it holds.
+ *   another agent   a cell of type agent (10) with colour c <= 5 and state d draws overlay = 1 + 4*c + ((d - D + 3) & 3): d is the
+ *                other agent's world direction, D the viewer's.  It is drawn over the empty tile (the observation does not say
+ *                what lies beneath).  A colour above 5 draws no overlay.
+ *   the viewer's own cell   draws the appearance of what the cell holds -- the carried object (utils/obs.py:204-207) -- under
+ *                overlay = 1 + 4*own_colour + 3 (no overlay for an own colour above 5, as in the full frame).  The viewer is
+ *                always drawn: the frame is a pure function of (image, direction, colour), so a terminated viewer looks like a
+ *                live one.
+ *   highlight    = (type != unseen) with MGX_VIEWS_HIGHLIGHT, MiniGrid's POV convention; 0 without.  Unseen cells draw the plain
+ *                empty tile.
+ * Any byte values are legal input: the direction counts as dir & 3, and the key is always in [0, 2500).
+ *
+ *   mgx_render_atlas_planar  atlas u8[2500, 3, tile_size, tile_size]: mgx_render_atlas' pixels, one plane per channel.
+ *   mgx_render_views   obs u8[n_views, v, v, 3] (v = spec->view_size, the only member read), dir u8[n_views], color
+ *                      u8[color_period]: view k has the own colour color[k % color_period] (the views of a trace [T, B, A, ...] need
+ *                      only the B*A colours).  frames u8[n_views, P, P, 3], P = v * tile_size, from the atlas of mgx_render_atlas;
+ *                      with MGX_VIEWS_PLANAR u8[n_views, 3, P, P] from the atlas of mgx_render_atlas_planar.  All offsets are 64-bit.
+ *                      With tile_size % 4 == 0 and `frames` 16-byte aligned the frames are written by 16-byte stores (non-temporal
+ *                      unless MGX_RENDER_STORES=plain, as mgx_render), otherwise by byte stores: same bytes.
+ * Return codes: NULL spec, n_views < 0, tile_size outside 1..64, color_period < 1, an unknown flag, view_size even or outside
+ * 3..MGX_MAX_VIEW: MGX_ERR_INVALID_ARGUMENT; then n_views == 0: MGX_OK, nothing is launched; then a NULL pointer:
+ * MGX_ERR_INVALID_ARGUMENT; more than INT_MAX workgroups: MGX_ERR_UNSUPPORTED.  Neither function synchronises. */
+enum { MGX_VIEWS_HIGHLIGHT = 1, MGX_VIEWS_PLANAR = 2 };
+int mgx_render_atlas_planar(int32_t tile_size, uint8_t *atlas, void *stream);
+int mgx_render_views(const MgxSpec *spec, int64_t n_views, const uint8_t *obs, const uint8_t *dir, const uint8_t *color,
+                     int64_t color_period, const uint8_t *atlas, int32_t tile_size, uint32_t flags, uint8_t *frames, void *stream);
+
 /* EPISODE ACCOUNTING (additive to ABI 11): the return, the length and the outcome of every episode, kept on the device beside the
  * envs -- what a consumer of the reference's step() return values adds up from `rewards`, `terminations` and `truncations`
  * (multigrid/base.py:338-340) and logs when an episode ends.  Build-defined like the auto-reset it follows: the reference has no

@@ -20,9 +20,10 @@ from .rllib import RLlibWrapper, to_rllib_env  # noqa: F401,E402
 __all__ += ["Agent", "MultiGridEnv", "CONFIGURATIONS", "BlockedUnlockPickupEnv", "EmptyEnv", "LockedHallwayEnv", "PlaygroundEnv",
             "RedBlueDoorsEnv", "make", "spec_for",
             "RLlibWrapper", "to_rllib_env"]
-from .wrappers import FullyObsWrapper, ImgObsWrapper, OneHotObsWrapper, SingleAgentWrapper  # noqa: F401,E402
+from .wrappers import (FullyObsWrapper, ImgObsWrapper, OneHotObsWrapper, RGBImgPartialObsWrapper,  # noqa: F401,E402
+                       SingleAgentWrapper)
 
-__all__ += ["FullyObsWrapper", "ImgObsWrapper", "OneHotObsWrapper", "SingleAgentWrapper"]
+__all__ += ["FullyObsWrapper", "ImgObsWrapper", "OneHotObsWrapper", "RGBImgPartialObsWrapper", "SingleAgentWrapper"]
 from .world import Ball, Box, Door, Floor, Goal, Grid, Key, Lava, Wall, WorldObj  # noqa: F401,E402
 from .mission import MissionSpace  # noqa: F401,E402
 

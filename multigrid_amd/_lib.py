@@ -30,7 +30,8 @@ EXPORTS = ("mgx_abi_version", "mgx_error_string", "mgx_last_hip_error", "mgx_gen
            "mgx_persistent_waves", "mgx_step_persistent", "mgx_persistent_post", "mgx_persistent_wait", "mgx_persistent_feed",
            "mgx_rollout_info", "mgx_render_atlas", "mgx_render", "mgx_reset_select", "mgx_reset_generate_select",
            "mgx_episode_stats", "mgx_episode_restart", "mgx_env_copy", "mgx_state_key", "mgx_obs_key", "mgx_action_mask",
-           "mgx_distance", "mgx_key_insert", "mgx_key_lookup", "mgx_select_work_bytes", "mgx_select")
+           "mgx_distance", "mgx_key_insert", "mgx_key_lookup", "mgx_select_work_bytes", "mgx_select",
+           "mgx_render_atlas_planar", "mgx_render_views")
 
 
 class MgxLaunchInfo(C.Structure):
@@ -126,6 +127,7 @@ class MgxKeyTableC(C.Structure):
     _fields_ = [("capacity", C.c_int64)] + [(n, C.c_void_p) for n in ("keys", "tag", "born", "visits", "ctrl")]
 
 
+VIEWS_HIGHLIGHT, VIEWS_PLANAR = 1, 2                         # mgx_render_views' flags (MGX_VIEWS_*)
 KEY_NO_COUNT = 1                                             # mgx_key_insert's flag (MGX_KEY_NO_COUNT)
 KEY_MAX_PROBE, KEY_MIN_CAPACITY, KEY_MAX_CAPACITY, KEY_CTRL_WORDS = 1024, 64, 1 << 30, 8      # MGX_KEY_*
 KEY_CTRL_ENTRIES, KEY_CTRL_DROPPED = 2, 3                    # the control words a caller reads (MGX_KEY_CTRL_*)
@@ -263,6 +265,12 @@ def lib() -> C.CDLL:
         L.mgx_select_work_bytes.argtypes = [i64]
         L.mgx_select.restype = C.c_int
         L.mgx_select.argtypes = [i64, vp, vp, vp, i64, i64, vp, vp, vp, C.c_size_t, vp]
+    # (... or the view frames: only render_views() needs them)
+    if is_product_lib() or hasattr(L, "mgx_render_views"):
+        L.mgx_render_atlas_planar.restype = C.c_int
+        L.mgx_render_atlas_planar.argtypes = [C.c_int32, vp, vp]
+        L.mgx_render_views.restype = C.c_int
+        L.mgx_render_views.argtypes = [C.POINTER(MgxSpecC), i64, vp, vp, vp, i64, vp, C.c_int32, C.c_uint32, vp, vp]
     if L.mgx_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH}: ABI version {L.mgx_abi_version()} != {ABI_VERSION}; rebuild it")
     _lib = L

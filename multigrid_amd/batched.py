@@ -1067,6 +1067,81 @@ class BatchedMultiGridEnv:
         self.backend.render(n, cells, agents, obs, ts, out)
         return out
 
+    def render_views(self, obs: torch.Tensor | None = None, dir: torch.Tensor | None = None, *, env_ids=None, colors=None,
+                     tile_size: int = 8, highlight: bool = True, channels_first: bool = False,
+                     out: torch.Tensor | None = None) -> torch.Tensor:
+        """Every agent's view as the RGB frame it sees, u8[..., A, P, P, 3] on the device with P = view_size * tile_size (or
+        u8[..., A, 3, P, P] with `channels_first`, what a torch CNN takes): the partial pixel observation of MiniGrid's
+        RGBImgPartialObsWrapper, by the rule of include/mgx.h "VIEW FRAMES" -- the viewer at the bottom centre facing up, other
+        agents turned by the viewer's direction, the carried object under the viewer, unseen cells dark.  ONE launch.
+
+        obs, dir   None: the env's own latest outputs, frames u8[B, A, ...].  Otherwise contiguous uint8 tensors [..., A, v, v, 3] and
+                   [..., A] on the env's device -- a rollout's [T, B, A, ...] is one launch.
+        colors     each viewer's own colour: a contiguous uint8 tensor of `dir`'s shape.  None: the env's agent colours u8[B, A], for
+                   which the leading dimensions must end in [B, A].
+        env_ids    instead of `obs`: a contiguous int64 [n] tensor on the env's device.  Those envs are observed into a private buffer
+                   first, as render(highlight=True) does, so a restored or forked env is drawn without stepping it: frames
+                   u8[n, A, ...].  Its form is checked, its values are not (no host round trip): an id outside [0, batch) is clamped
+                   into the batch.
+        highlight  shade every cell the agent sees; out: a contiguous uint8 tensor of the result's shape on this device to write into.
+        The env's state and every buffer it has handed out are left as they are.  Tiles come from an atlas rendered once per (device,
+        tile_size, layout): the first call for one renders it, every later call can be captured in a graph."""
+        self._no_session("render_views")
+        ts, sp = int(tile_size), self.spec
+        if not 1 <= ts <= 64:
+            raise ValueError(f"render_views: tile_size must be in 1..64, got {tile_size}")
+        A, v = sp.num_agents, sp.view_size
+        if (obs is None) != (dir is None):
+            raise ValueError("render_views: obs and dir go together")
+        if env_ids is not None:
+            if obs is not None:
+                raise ValueError("render_views: env_ids and obs exclude each other")
+            self._need_state()
+            self.join()
+            ids = self._index_arg("render_views", "env_ids", env_ids).clamp(0, self.batch - 1)
+            n = int(ids.shape[0])
+            cells, agents = self._cells.index_select(0, ids), self.agents.index_select(0, ids)
+            scratch = getattr(self, "_render_scratch", None)
+            if scratch is None or scratch[0].shape[0] < n:
+                scratch = (torch.empty((n,) + tuple(self.obs.shape[1:]), dtype=torch.uint8, device=self.device),
+                           torch.empty((n, A), dtype=torch.uint8, device=self.device))
+                self._render_scratch = scratch
+            obs, dir = scratch[0][:n], scratch[1][:n]
+            if n:
+                self.backend.gen_obs(n, cells, agents, obs, dir)
+            if colors is None:
+                colors = agents[:, :, 0].contiguous()
+        elif obs is None:
+            self._need_state()
+            self.join()
+            obs, dir = self.obs, self.dir
+        for name, t, tail in (("obs", obs, (A, v, v, 3)), ("dir", dir, (A,))):
+            if not torch.is_tensor(t) or t.dtype != torch.uint8 or t.device != self.device or not t.is_contiguous() \
+                    or tuple(t.shape[-len(tail):]) != tail:
+                raise ValueError(f"render_views: {name} must be a contiguous uint8 tensor [..., {', '.join(map(str, tail))}] on {self.device}")
+        lead = tuple(dir.shape)
+        if tuple(obs.shape[:-3]) != lead:
+            raise ValueError(f"render_views: obs {tuple(obs.shape)} and dir {lead} disagree in their leading dimensions")
+        if colors is None:
+            if lead[-2:] != (self.batch, A):
+                raise ValueError(f"render_views: the env's agent colours are [{self.batch}, {A}] and dir is {lead}: pass colors=")
+            self._need_state()
+            colors = self.agents[:, :, 0].contiguous()
+        elif not torch.is_tensor(colors) or colors.dtype != torch.uint8 or colors.device != self.device \
+                or not colors.is_contiguous() or tuple(colors.shape) != lead:
+            raise ValueError(f"render_views: colors must be a contiguous uint8 tensor of dir's shape {lead} on {self.device}")
+        P = v * ts
+        shape = lead + ((3, P, P) if channels_first else (P, P, 3))
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        elif (not torch.is_tensor(out) or tuple(out.shape) != shape or out.dtype != torch.uint8 or out.device != self.device
+              or not out.is_contiguous()):
+            raise ValueError(f"render_views: out must be a contiguous uint8 tensor of shape {shape} on {self.device}")
+        n_views = dir.numel()
+        if n_views:
+            self.backend.render_views(n_views, obs, dir, colors, ts, bool(highlight), bool(channels_first), out)
+        return out
+
     def set_layout_pool(self, grids, agents, auxs=None):
         """Pool of K pre-generated episode starts for `reset_done()`: u8[K,H,W,3], u8[K,A,8], u8[K,16] | None."""
         self._no_session("set_layout_pool")

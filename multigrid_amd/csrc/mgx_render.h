@@ -82,6 +82,22 @@ MGX_RHD int render_appearance(uint32_t t, uint32_t c, uint32_t s) {
 // the atlas index of a key
 MGX_RHD int render_key(int appearance, int overlay, int highlight) { return (appearance * RENDER_OVERLAYS + overlay) * 2 + highlight; }
 
+// The key of one cell of an agent's VIEW drawn as the viewer sees it (include/mgx.h "VIEW FRAMES"): cell bytes (t, c, s) of
+// image[i, j], `own` = the viewer's cell (v / 2, v - 1).  The viewer faces up in its view (direction 3), so another agent -- a
+// cell of type `agent` (10) whose state byte is its world direction -- is turned by the viewer's direction: (s - dir + 3) & 3,
+// over the empty tile (the observation does not say what lies under it).  The viewer's own cell holds what it carries
+// (utils/obs.py:204-207) and always draws the viewer; a colour above 5 has no overlay, as in the full frame.  Highlighting
+// (MiniGrid's POV convention) shades every cell that is not `unseen`; an unseen cell draws the plain empty tile.  Any bytes are
+// legal: only dir & 3 counts, and the key is below RENDER_KEYS for every input.
+MGX_RHD int render_view_key(uint32_t t, uint32_t c, uint32_t s, bool own, uint32_t viewer_dir, uint32_t viewer_color, bool highlight) {
+    int ov = 0;
+    if (own)
+        ov = viewer_color <= 5u ? 1 + 4 * (int)viewer_color + 3 : 0;
+    else if (t == 10u && c <= 5u)
+        ov = 1 + 4 * (int)c + (int)((s - viewer_dir + 3u) & 3u);
+    return render_key(render_appearance(t, c, s), ov, highlight && t != 0u ? 1 : 0);
+}
+
 // multigrid/core/constants.py:12-19 COLORS
 MGX_RHD uint32_t render_rgb(int color) {
     switch (color) {

@@ -495,6 +495,33 @@ class HipBackend(KeyTableOps, SelectOps):
             _ATLASES[key] = atlas
         return atlas
 
+    def render_atlas_planar(self, tile_size: int) -> torch.Tensor:
+        """u8[2500, 3, ts, ts]: the atlas' pixels with one plane per channel (include/mgx.h mgx_render_atlas_planar), what the
+        channels-first view frames are copied from; cached per (device, tile_size, layout)."""
+        key = (self.device.index if self.device.index is not None else torch.cuda.current_device(), int(tile_size), "planar")
+        atlas = _ATLASES.get(key)
+        if atlas is None:
+            if not 1 <= int(tile_size) <= RENDER_MAX_TILE:
+                raise ValueError(f"tile_size must be in 1..{RENDER_MAX_TILE}, got {tile_size}")
+            atlas = torch.empty((RENDER_KEYS, 3, tile_size, tile_size), dtype=torch.uint8, device=self.device)
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().mgx_render_atlas_planar(int(tile_size), atlas.data_ptr(), _stream(self.device)),
+                           "mgx_render_atlas_planar")
+            _ATLASES[key] = atlas
+        return atlas
+
+    def render_views(self, n_views, obs, dirs, colors, tile_size, highlight, planar, frames):
+        """frames u8[n_views, P, P, 3] (planar: u8[n_views, 3, P, P]) of the views obs u8[n_views, v, v, 3] / dirs u8[n_views]; view k
+        has the own colour colors[k % colors.numel()] (include/mgx.h "VIEW FRAMES").  The first call for a (tile_size, layout)
+        renders its atlas; later ones are one launch."""
+        atlas = self.render_atlas_planar(tile_size) if planar else self.render_atlas(tile_size)
+        flags = (_lib.VIEWS_HIGHLIGHT if highlight else 0) | (_lib.VIEWS_PLANAR if planar else 0)
+        with torch.cuda.device(frames.device):
+            rc = _lib.lib().mgx_render_views(C.byref(self.sc), n_views, obs.data_ptr(), dirs.data_ptr(), colors.data_ptr(),
+                                             colors.numel(), atlas.data_ptr(), int(tile_size), flags, frames.data_ptr(),
+                                             _stream(frames.device))
+        _lib.check(rc, "mgx_render_views")
+
     def render(self, n, grid, agents, obs, tile_size, frames):
         """frames u8[n, H*ts, W*ts, 3] of the n envs `grid` / `agents`; `obs` = their gen_obs observation (highlight) or None."""
         atlas = self.render_atlas(tile_size)

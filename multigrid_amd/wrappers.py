@@ -93,6 +93,36 @@ class OneHotObsWrapper(_ObservationWrapper):
         return obs
 
 
+class RGBImgPartialObsWrapper(_ObservationWrapper):
+    """MiniGrid's RGBImgPartialObsWrapper for several agents: every agent's 'image' becomes its own view as pixels, uint8
+    (v * tile_size, v * tile_size, 3), drawn on the device (`BatchedMultiGridEnv.render_views`; the rule: include/mgx.h "VIEW
+    FRAMES").  The reference has no such wrapper (its get_pov_render refuses several agents)."""
+
+    def __init__(self, env, tile_size: int = 8):
+        super().__init__(env)
+        self.tile_size = int(tile_size)
+        for agent in self.env.unwrapped.agents:
+            h, w, _ = agent.observation_space["image"].shape
+            agent.observation_space["image"] = Box(low=0, high=255, shape=(h * self.tile_size, w * self.tile_size, 3), dtype=np.uint8)
+
+    def observation(self, obs):
+        import torch
+        base = self.env.unwrapped
+        benv = base._benv
+        if self.env is base:
+            # directly over the env: its partial views are still in HBM, draw them there
+            frames = benv.render_views(tile_size=self.tile_size)[0].cpu().numpy()
+        else:
+            # over another wrapper: draw the images handed in (they must still be (v, v, 3) views)
+            ids = sorted(obs)
+            img = torch.from_numpy(np.stack([np.asarray(obs[i]["image"]) for i in ids]).astype(np.uint8)).to(benv.device)
+            d = torch.from_numpy(np.array([int(obs[i]["direction"]) for i in ids], np.uint8)).to(benv.device)
+            frames = dict(zip(ids, benv.render_views(img[None], d[None], tile_size=self.tile_size)[0].cpu().numpy()))
+        for agent_id in obs:
+            obs[agent_id]["image"] = frames[agent_id]
+        return obs
+
+
 class SingleAgentWrapper:
     """multigrid/wrappers.py:193-233: single-agent view of a one-agent env (plain obs / action instead of dicts)."""
 
